@@ -14,6 +14,7 @@ steps, so the timed region needs no alignment: exactly W warm-up steps run, then
 timed.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--strategy zero2|ddp|fsdp|zero3]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Launch modes (reference: scripts/launch_multi.sh:38-82 starts one pod per rank; here one process
@@ -29,6 +30,12 @@ per GPU on one node):
 
 K steps are timed between a barrier + torch.cuda.synchronize() on both sides; the time is the MAX over
 ranks; rank 0 prints one JSON line.  ``value`` is the whole-job tokens/s over all N GPUs.
+
+A plain run does only that: set up, W warm-up steps, K timed steps, the JSON line.  ``--dump-outputs DIR``
+then also writes the timed steps' results (losses, a seeded sample of the trained parameters) as ``.npy``
+files; weights, tokens and dropout seeds are seeded, so two runs with the same arguments start from the
+same inputs.  Extra measurements are options of their own (``--host-check``, ``--emulate N``); ``--full``
+is the switch for any that would otherwise ride along with a plain run (none today).
 """
 import argparse
 import json
@@ -100,7 +107,50 @@ def build_parser():
     ap.add_argument("--host-check", action="store_true",
                     help="after the timed steps: host enqueue time per step while the GPU is held busy "
                          "(is the eager step host-bound?)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed as DIR/<name>.npy (float32): the last "
+                         "timed step's loss, every timed step's loss, and a fixed seeded sample of the trained "
+                         "fp32 parameters; the inputs are the same from run to run, so two builds compare "
+                         "array for array")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure.  A plain run only sets up, warms "
+                         "up, times --steps steps and prints the JSON line; every extra measurement this "
+                         "benchmark has is an option of its own (--host-check, --emulate), so today --full "
+                         "adds nothing to them")
     return ap
+
+
+DUMP_PARAM_ELEMS = 8 << 20     # --dump-outputs keeps at most this many parameter elements (32 MiB of float32)
+
+
+def dump_outputs(dirname, engine, loss, loss_hist, rank):
+    """``--dump-outputs``: what a caller of the timed micro-steps holds after the last one.
+    ``loss.npy`` is the loss the last timed step returned, ``loss_history.npy`` the loss of every timed
+    step, ``params_sample.npy`` the fp32 master parameters those steps trained: whole when they fit
+    DUMP_PARAM_ELEMS, else per tensor (in name order) the elements at indices drawn from a generator
+    seeded with 0, so every run and every build samples the same elements.  Every rank takes part (the
+    full parameters are gathered); rank 0 writes."""
+    import numpy as np
+    import torch
+    params = engine.full_state_dict()
+    if rank != 0:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(t.numel() for t in params.values())
+    rng = np.random.default_rng(0)
+    parts = []
+    for name in sorted(params):
+        flat = params[name].detach().reshape(-1)
+        if total > DUMP_PARAM_ELEMS:
+            k = max(1, flat.numel() * DUMP_PARAM_ELEMS // total)
+            idx = np.sort(rng.integers(0, flat.numel(), size=k))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        parts.append(flat.float().cpu().numpy())
+    arrays = {"loss": loss.detach().float().reshape(()).cpu().numpy(),
+              "loss_history": loss_hist.detach().float().cpu().numpy(),
+              "params_sample": np.concatenate(parts) if parts else np.zeros(0, np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 def _model_name(tier, c):
@@ -312,6 +362,8 @@ def run_rank(args) -> int:
         final_loss = float(loss.item())
         peak_gb = torch.cuda.max_memory_allocated(device) / 1e9 if cuda else 0.0
         peak_gb = all_reduce_max(peak_gb, device)
+        if args.dump_outputs:                # after the peak is read: the gathered fp32 copy is no part of the run
+            dump_outputs(args.dump_outputs, engine, loss, loss_hist[:args.steps], rank)
         phases = timers.summary() if timers is not None else None
         comm_wait = all_reduce_max(phases["comm_wait"], device) if phases else 0.0
         graphed = bool(runner is not None and runner.graphs and not runner.disabled)

@@ -82,6 +82,60 @@ def test_bench_single_process_cpu():
     assert rec["n_gpus"] == rec["world_size_seen"] == 1 and rec["wire_bytes_per_step"] == 0
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """``--dump-outputs DIR`` writes the timed steps' results as float32 ``.npy`` files, the same from run
+    to run (same seeded inputs); ``--steps`` is the number of timed steps; ``--full`` is accepted."""
+    import numpy as np
+    runs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = subprocess.run(BASE + ["--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)] + extra,
+                           capture_output=True, text=True, env=_env(), timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        recs = _json_lines(r.stdout)
+        assert len(recs) == 1 and recs[0]["steps"] == 3 and recs[0]["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["loss.npy", "loss_history.npy", "params_sample.npy"]
+        arrs = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["loss"].shape == () and arrs["loss_history"].shape == (3,)
+        assert arrs["loss_history"][-1] == arrs["loss"]
+        assert abs(float(arrs["loss"]) - recs[0]["final_loss"]) < 1e-6 * abs(recs[0]["final_loss"])
+        assert arrs["params_sample"].size == recs[0]["trainable_params"]      # tiny model: dumped whole
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        runs.append(arrs)
+    for k in runs[0]:       # fp32 on the CPU: same inputs, same arithmetic up to the threads' summation order
+        np.testing.assert_allclose(runs[0][k], runs[1][k], rtol=1e-4, atol=1e-6)
+
+
+def test_dump_outputs_samples_large_models():
+    """Above DUMP_PARAM_ELEMS parameters the dump is a fixed sample: same elements on every call."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Eng:
+        def full_state_dict(self):
+            g = torch.Generator().manual_seed(1)
+            return {"b": torch.randn(3, 5, generator=g), "a": torch.randn(40, generator=g)}
+
+    import numpy as np
+    import tempfile
+    old = bench.DUMP_PARAM_ELEMS
+    bench.DUMP_PARAM_ELEMS = 11
+    try:
+        outs = []
+        for _ in range(2):
+            with tempfile.TemporaryDirectory() as d:
+                bench.dump_outputs(d, Eng(), torch.tensor(2.5), torch.tensor([3.0, 2.5]), 0)
+                outs.append(np.load(os.path.join(d, "params_sample.npy")))
+    finally:
+        bench.DUMP_PARAM_ELEMS = old
+    full = Eng().full_state_dict()
+    assert outs[0].dtype == np.float32 and outs[0].size == 40 * 11 // 55 + 15 * 11 // 55
+    assert np.array_equal(outs[0], outs[1])
+    assert set(outs[0][:8]) <= set(full["a"].numpy()) and set(outs[0][8:]) <= set(full["b"].numpy().ravel())
+
+
 def test_bench_prediction_lookup():
     """The shipped emulated-fabric table row for a configuration (what a real N-GPU line is compared to)."""
     sys.path.insert(0, ROOT)
