@@ -6,7 +6,8 @@
 //   NT: A stored [M][K], B stored [N][K]  (both K-contiguous)  forward x W^T, dgrad dY (W^T)^T
 //   TN: A stored [K][M], B stored [K][N]  (both K-strided)     wgrad dY^T X
 // so both operands of one kernel use the same fragment read (row_frag for NT, tr_frag for TN) and
-// therefore the same k order inside an MFMA (mfma_tiles.h).
+// therefore the same k order inside an MFMA (mfma_tiles.h).  The mixed layout (A K-contiguous, B
+// K-strided) is gemm_nn.hip, which makes the two orders agree when it stages B.
 //
 // Block = 4 waves (2 x 2), tile BM x BN x 64.  Per 64-deep k-step each wave does 4 k16 steps of
 // (BM/64) x (BN/64) v_mfma_f32_32x32x16_bf16; A and B tiles are double-buffered in LDS and filled by
@@ -17,27 +18,11 @@
 // contiguous run of tiles sharing A rows in its L2).  Optional split-K writes fp32 partials
 // reduced by a second kernel (small grids: out-proj / wgrad of 1024 x 1024).
 #include "common.h"
+#include "gemm_common.h"
 #include "launchers.h"
 #include "mfma_tiles.h"
 
 namespace {
-
-constexpr int kBK = 64;
-
-struct GemmArgs {
-  const bf16_t* a;
-  const bf16_t* b;
-  bf16_t* c;
-  const bf16_t* bias;
-  const float* alpha;   // optional device scalar multiplying A B (before bias / accumulate)
-  float* part;          // split-K partials [splits][M][N] (fp32), null without split-K
-  long lda, ldb, ldc;
-  int M, N, K;
-  int accumulate;
-  int ksplit;           // K range per split (multiple of kBK)
-  int pf;               // L2 prefetch distance in k-steps (PF kernels)
-  int gm;               // tile order: groups of gm row-blocks (each XCD's run covers gm x (run / gm) tiles)
-};
 
 // tile image geometry: NT -> rows = m (or n), 64 k per row (D = 64 image, BM rows);
 //                      TN -> rows = k (64), BM (or BN) m per row (D = BM image, 64 rows)
@@ -192,35 +177,6 @@ __global__ __launch_bounds__(256, NSTAGE == 2 ? 2 : 1) void gemm_kernel(GemmArgs
   }
 }
 
-// split-K reduction: C = sum_s part[s] (+ bias) (+ C)
-__global__ __launch_bounds__(256) void gemm_splitk_reduce(GemmArgs g, int splits) {
-  const long total4 = (long)g.M * g.N / 4;
-  const float al = g.alpha ? *g.alpha : 1.f;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
-    const long e = i * 4;
-    const int m = (int)(e / g.N), n = (int)(e % g.N);
-    float4 s = *reinterpret_cast<const float4*>(g.part + e);
-    for (int k = 1; k < splits; ++k) {
-      const float4 t = *reinterpret_cast<const float4*>(g.part + (size_t)k * g.M * g.N + e);
-      s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
-    }
-    float v[4] = {s.x * al, s.y * al, s.z * al, s.w * al};
-    if (g.bias) {
-      const uint2 bb = *reinterpret_cast<const uint2*>(g.bias + n);
-      v[0] += lo_bf(bb.x); v[1] += hi_bf(bb.x); v[2] += lo_bf(bb.y); v[3] += hi_bf(bb.y);
-    }
-    bf16_t* cp = g.c + (size_t)m * g.ldc + n;
-    if (g.accumulate) {
-      const uint2 old = *reinterpret_cast<const uint2*>(cp);
-      v[0] += lo_bf(old.x); v[1] += hi_bf(old.x); v[2] += lo_bf(old.y); v[3] += hi_bf(old.y);
-    }
-    uint2 o;
-    o.x = pack_bf2(v[0], v[1]);
-    o.y = pack_bf2(v[2], v[3]);
-    *reinterpret_cast<uint2*>(cp) = o;
-  }
-}
-
 template <int BM, int BN, bool TN, bool PF, int NSTAGE>
 void launch_ns(const GemmArgs& g, int splits, hipStream_t st) {
   constexpr int smem = NSTAGE * Geo<BM, BN, TN>::STAGE + (PF ? 1024 : 0);
@@ -285,11 +241,7 @@ int dltb_gemm(const void* a, const void* b, void* c, const void* bias, float* pa
   g.N = N;
   g.K = K;
   g.accumulate = accumulate;
-  if (splits < 1) splits = 1;
-  const int kchunks = K / kBK;
-  if (splits > kchunks) splits = kchunks;
-  g.ksplit = ((kchunks + splits - 1) / splits) * kBK;
-  splits = (K + g.ksplit - 1) / g.ksplit;
+  g.ksplit = gemm_ksplit(K, splits);
   g.part = splits > 1 ? part : nullptr;
   if (splits > 1 && !part) return -1;
 #define DLTB_G(BM, BN)                                              \

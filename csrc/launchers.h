@@ -149,6 +149,12 @@ int dltb_gemm(const void* a, const void* b, void* c, const void* bias, float* pa
               long ldc, int M, int N, int K, bool tn, int accumulate, int splits, int cfg, int pf, int gm,
               const float* alpha, hipStream_t st, int stages = 0);
 
+// ---- gemm_nn.hip: C[M,N] = alpha A B; A [M][K], B [K][N] (the tied head's dgrad without a transposed W);
+// cfg 0 = 128x128, 1 = 256x128, 2 = 64x64 tiles; returns the split count used, -1 when refused
+bool dltb_gemm_nn_supported(int M, int N, int K, int cfg);
+int dltb_gemm_nn(const void* a, const void* b, void* c, float* part, long lda, long ldb, long ldc, int M, int N,
+                 int K, int splits, int cfg, int gm, const float* alpha, hipStream_t st);
+
 // ---- gemm_tn.hip: C[b][M][N] (+)= A[b][K][M]^T B[b][K][N] (weight gradients dY^T X), bf16, 256 x 256 tiles,
 // M, N multiples of 256, K of 64 (>= 128)
 bool dltb_gemm_tn_supported(int M, int N, int K);

@@ -164,17 +164,34 @@ DLTB_DEV void wait_vm() {
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
 }
 
-template <int D, int ROWS, bool ASM = false>
+// Fragment k order, and how a kernel with one K-contiguous and one K-strided operand (gemm_nn.hip)
+// makes them agree.  Inside one 16-deep MFMA step, element j (0..7) of lane half h holds
+//     row_frag:  k = 8 h + j                         (ds_read_b128 of chunk 2s + h)
+//     tr_frag:   k = (j & 3) + 8 (j >> 2) + 4 h      (image rows row_base + k)
+// and the two MFMA operands must pair equal k.  tr_frag's k is row_frag's with bits 2 and 3 swapped,
+// and the source address of an LDS-DMA is free per lane, so a K-strided image staged with KSWAP
+// holds source row swap23(r) in image row r: tr_frag then delivers k = 8 h + j, row_frag's order,
+// at no cost in the loop and with the LDS addresses (hence the banking) of the plain image.
+// The alternative, reading the K-contiguous image in tr_frag's order (2 x ds_read_b64: the h-th
+// 8-byte half of chunks 2s and 2s + 1 of the lane's row), is 2-way bank-conflicted under swz<64>:
+// ds_read_b64 banks per 32-lane half (one h), the half's 32 rows fall on 16 distinct 16-byte slots
+// (swz reads row bits 1..3 only, rows r and r + 16 share a slot at different addresses) and use one
+// 8-byte half of each, i.e. 32 of the 64 banks.
+DLTB_DEV int swap23(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
+
+template <int D, int ROWS, bool ASM = false, bool KSWAP = false>
 struct GldsTile {
   static constexpr int CH = D / 8;
   static constexpr int NI = ROWS * CH / 256;   // wave-instructions per wave (4 waves per tile)
   static_assert(ROWS * CH % 256 == 0, "tile must split into whole wave-instructions");
+  static_assert(!KSWAP || ROWS % 16 == 0, "swap23 permutes rows within aligned groups of 16");
   DLTB_DEV static void load(const bf16_t* base, long stride, int row0, char* tile, int wv, int lane) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int lin = (wv * NI + i) * 64 + lane;
       const int row = lin / CH, pos = lin % CH;
-      const bf16_t* src = base + (long)(row0 + row) * stride + ((pos ^ swz<D>(row)) << 3);
+      const int srow = KSWAP ? swap23(row) : row;   // image row `row` (swizzled as such) <- source row srow
+      const bf16_t* src = base + (long)(row0 + srow) * stride + ((pos ^ swz<D>(row)) << 3);
       if constexpr (ASM)
         glds16_asm(src, tile + (wv * NI + i) * 1024);
       else
@@ -185,6 +202,7 @@ struct GldsTile {
   }
   // per-lane byte offsets of the NI DMA instructions relative to row row0 (tile-invariant)
   DLTB_DEV static void offsets(long stride, int wv, int lane, uint32_t (&off)[NI]) {
+    static_assert(!KSWAP, "the hoisted-offset form has no row permutation");
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int lin = (wv * NI + i) * 64 + lane;

@@ -29,6 +29,7 @@ from .models import build_model, get_model_config
 from .parallel.checkpoint import export_consolidated, load_checkpoint, save_checkpoint
 from .parallel.graphs import GraphedStep, graphs_enabled
 from .ops._ext import available as ext_available, so_path
+from .ops import functional as _functional
 from .ops.functional import torch_fallbacks
 from .comm import describe as comm_describe
 from .parallel import STRATEGIES, engine_config, make_engine
@@ -109,6 +110,8 @@ def build_parser():
                    help="replay micro-steps as captured HIP graphs (parallel/graphs.py; off with --profile)")
     p.add_argument("--tunableop", default="auto", choices=["auto", "use", "tune", "off"],
                    help="hipBLASLt GEMM solutions (TunableOp results shipped in configs/tunableop)")
+    p.add_argument("--strict-kernels", action="store_true",
+                   help="a GPU product that would run as a plain torch GEMM (torch_gemm_fallbacks) is an error")
     return p
 
 
@@ -161,6 +164,7 @@ def train(args):
                                args.timeout_min, args.debug_collectives)
     is_main = rank == 0
     fabric = None
+    strict_before = _functional.strict_kernels       # --strict-kernels holds for this run only
     if auto_bucket:
         from .comm.topology import calibrate_fabric, measured_params, recommend_bucket_mb
         if (world > 1 and measured_params(world)[2] == "default"
@@ -169,6 +173,7 @@ def train(args):
             fabric = calibrate_fabric(device, sizes_mb=(4, 16, 64) if device.type == "cuda" else (0.25, 1.0))
         args.bucket_mb = recommend_bucket_mb(world)
     try:
+        _functional.strict_kernels = strict_before or bool(getattr(args, "strict_kernels", False))
         if device.type == "cuda" and not ext_available():
             raise RuntimeError("dltb._C is not built: run `python csrc/build.py` (the GPU path has no fallback)")
         gemm_mode = setup_tunableop(args.tunableop if (args.tunableop != "tune" or is_main) else "use") \
@@ -334,6 +339,7 @@ def train(args):
             "grad_comm_dtype": getattr(engine, "grad_comm_dtype", args.grad_comm_dtype), "strategy_engine": args.strategy, "bucket_mb": args.bucket_mb, "data_loader": args.data_loader,
             "kernels": so_path(), "platform": device_info(device), "gemm_tuning": gemm_mode,
             "torch_gemm_fallbacks": dict(torch_fallbacks) or None,
+            "strict_kernels": bool(_functional.strict_kernels),
             "phase_times_ms": timers.summary() if timers is not None else None,
             "loss_scaler": engine.scaler.stats() if engine.scaler is not None else None,
             "deepspeed_config_keys": ecfg.extra.get("ds_keys") or None,
@@ -347,6 +353,7 @@ def train(args):
         flush_tunableop()
         return record, extended
     finally:
+        _functional.strict_kernels = strict_before
         cleanup_distributed()
 
 

@@ -395,7 +395,15 @@ def head_dgrad(dl, w, wt, g):
     small.  With a cached W^T both operands are K-contiguous: a tuned hipBLASLt split-K solution
     when the table has the problem (TinyGPT-A: 116 us vs 149 us for the own kernel + reduce,
     profiles/head_dgrad_blaslt_r2.txt), then g applied by one small scale kernel; otherwise the
-    own split-K MFMA GEMM with g as a device alpha in its split-K reduction."""
+    own split-K MFMA GEMM with g as a device alpha in its split-K reduction.
+
+    Without a cached W^T (FSDP, ZeRO-3 without resident parameters) and for every fp16 step, dL is
+    K-contiguous and W K-strided: the own NN-layout kernel (csrc/gemm_nn.hip) takes both as they
+    are, with g as its device alpha.  Tile and split rule (``_head_nn_plan``): the largest tile of
+    256 x 128, 128 x 128, 64 x 64 that divides the problem and gives at least 32 tiles, else the
+    smallest that divides it; then split K so that tiles x splits reaches the 256 CUs (at most 8
+    splits, none once the tiles alone cover the CUs).  A call whose dtype, layout or alignment does
+    not fit returns to the counted torch product; ``own_head_nn = False`` turns the branch off."""
     if _gpu(dl) and wt is not None and dl.stride(1) == 1 and dl.dtype == torch.bfloat16:
         M, K = dl.shape
         N = wt.shape[0]
@@ -406,16 +414,50 @@ def head_dgrad(dl, w, wt, g):
         C = ext()
         if C.gemm_supported(M, N, K, False, 2):
             return C.gemm(dl, wt, None, None, False, False, 4, 2, 0, 1, g)
+    if _gpu(dl) and own_head_nn:
+        plan = _head_nn_plan(dl, w, g)
+        if plan is not None:
+            return ext().gemm_nn(dl, w, None, plan[1], plan[0], 1, g)
     if _gpu(dl):
         _note_torch_fallback("head_dgrad", dl.shape, w.shape)
     return (torch.mm(dl, w) * g).to(dl.dtype)
 
 
+own_head_nn = True          # head_dgrad's NN-layout branch (False: the torch product, for A/Bs and tests)
+_NN_TILES = ((1, 256, 128), (0, 128, 128), (2, 64, 64))     # gemm_nn cfg, BM, BN: largest first
+_NN_CUS = 256
+
+
+def _head_nn_plan(dl, w, g):
+    """(cfg, splits) of gemm_nn for dX = g * dl w, or None when the call does not fit the kernel
+    (the rule is head_dgrad's docstring)."""
+    if not (dl.dim() == 2 and w.dim() == 2 and dl.dtype == w.dtype
+            and dl.dtype in (torch.bfloat16, torch.float16) and w.is_cuda and w.device == dl.device
+            and dl.shape[1] == w.shape[0] and dl.stride(1) == 1 and w.stride(1) == 1
+            and dl.stride(0) % 8 == 0 and w.stride(0) % 8 == 0
+            and dl.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
+            and torch.is_tensor(g) and g.is_cuda and g.dtype == torch.float32 and g.numel() >= 1):
+        return None
+    M, K = dl.shape
+    N = w.shape[1]
+    C = ext()
+    fit = [(cfg, (M // bm) * (N // bn)) for cfg, bm, bn in _NN_TILES if C.gemm_nn_supported(M, N, K, cfg)]
+    if not fit:
+        return None
+    cfg, tiles = next(((c, t) for c, t in fit if t >= 32), fit[-1])
+    return cfg, max(1, min(8, _NN_CUS // tiles, K // 64))
+
+
 torch_fallbacks = {}        # op -> calls that ran a torch GEMM on the GPU (reported by bench.py / the harness)
+strict_kernels = False      # True: a torch GEMM fallback on the GPU raises instead of being counted
 
 
 def _note_torch_fallback(op, *shapes):
-    """A GPU product that neither hipBLASLt's table nor an own kernel took: counted, and warned about once per op."""
+    """A GPU product that neither hipBLASLt's table nor an own kernel took: counted, and warned about
+    once per op; an error under ``strict_kernels``."""
+    if strict_kernels:
+        raise RuntimeError(f"dltb: {op} {shapes} would run as a plain torch GEMM on the GPU "
+                           "(no tuned or own kernel) and strict_kernels is set")
     n = torch_fallbacks.get(op, 0)
     torch_fallbacks[op] = n + 1
     if n == 0:

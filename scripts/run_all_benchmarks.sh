@@ -31,7 +31,7 @@
 #   env: STEPS, SEQ, SEQ_LIST (several sequence lengths: the vram_vs_seqlen plot), TIER, WS_LIST, STRATS,
 #        BENCHMARKS / BENCHMARKS_FILE (explicit "STRATEGY WS SEQ TIER STEPS" rows instead of the
 #        STRATS x SEQ_LIST x WS_LIST product, e.g. configs/suite/multiseq_1gpu.txt), TIMEOUT,
-#        HARNESS_EXTRA (extra harness flags),
+#        HARNESS_EXTRA (extra harness flags; --strict-kernels is always passed),
 #        M7B, M7B_WS, M7B_TIER, M7B_SEQ, M7B_STEPS (step 2b),
 #        FORCE_NPROC (process slots when no GPU is visible, e.g. the gloo/CPU rehearsal),
 #        COLLECTIVES=0 (skip step 1), COLL_MAX_MB (largest swept message, default 512)
@@ -41,7 +41,7 @@ RESULTS="${1:-$ROOT/results}"
 STEPS="${STEPS:-100}"; SEQ="${SEQ:-2048}"; TIER="${TIER:-A}"; TIMEOUT="${TIMEOUT:-900}"
 STRATS="${STRATS-ddp fsdp zero2 zero3 fsdp_root ddp_bf16 fsdp_bf16 ddp_uniform fsdp_uniform}"
 NGPU="${FORCE_NPROC:-$(python3 -c "import torch; print(torch.cuda.device_count())" 2>/dev/null || echo 0)}"
-read -r -a HX <<< "${HARNESS_EXTRA:-}"
+read -r -a HX <<< "--strict-kernels ${HARNESS_EXTRA:-}"   # a suite row that falls back to a torch GEMM fails
 WS_LIST="${WS_LIST:-1 2 4 8}"
 mkdir -p "$RESULTS/raw" "$RESULTS/summary"
 FAILED=(); DONE=0
