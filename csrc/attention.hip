@@ -87,6 +87,7 @@ struct AttnArgs {
   const int64_t* seed_ptr;
   int64_t site;
   int gsplit;       // bwd_dkdv: workgroups per KV head, each summing G / gsplit query heads
+  int window;       // WIN kernels: query i sees keys i - window < j <= i (0 < window < T; else unused)
   float* part;      // bwd_dkdv with gsplit > 1: fp32 partials [gsplit][2][B*T][Hkv*D] (scaled)
 };
 
@@ -176,6 +177,9 @@ __global__ __launch_bounds__(256) void attn_mask_kernel(uint32_t* __restrict__ m
 // tile's row max exceeds m by more than kRescaleLog2 (p <= 2^8, safe in f32 and bf16); the decision
 // is wave-uniform so the rescale is a branch, not per-tile work.  The causal mask is applied on
 // diagonal tiles only.  Dropout: on the packed bf16 pairs (pack_frag_keep).
+// WIN (causal only, its own instantiations): a sliding window P.window = W, query i sees keys i - W < j <= i.
+// The key tiles start at t_lo instead of 0, tiles below a wave's band are skipped, lower-edge tiles mask keys
+// <= query - W, and the online softmax handles rows / key splits that have seen no key yet (rescale_win).
 constexpr float kRescaleLog2 = 8.f;
 
 template <int I>
@@ -291,8 +295,9 @@ constexpr int fwd_stage_bytes() { return 2 * kTile * D * 2 + 1024; }   // K, V, 
 template <int D, int KS = fwd_ks<D>()>
 constexpr int fwd_smem_bytes() { return fwd_nst<D, KS>() * KS * fwd_stage_bytes<D>(); }
 
-template <int D, bool CAUSAL, bool DROP, int KS>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false>
 __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
+  static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
   constexpr int TB = kTile * D * 2;
   constexpr int NACC = D / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -314,7 +319,11 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
       qf[s] = scale_frag(__builtin_bit_cast(bfx8, ld16<uint4>(qrow + 16 * s + 8 * h)), P.scale * kLog2e);
   }
   const int nt = CAUSAL ? min(nT, (qb * kBlockRows + kBlockRows - 1) / kTile + 1) : nT;
-  const int nit = (nt + KS - 1) / KS;
+  // sliding window W: row qi sees keys qi - W < key <= qi, so the block's first row starts at key tile t_lo;
+  // the key splits are numbered from there (t = t_lo + it * KS + split)
+  const int W = WIN ? P.window : 0;
+  const int t_lo = WIN ? max(0, qb * kBlockRows - W + 1) / kTile : 0;
+  const int nit = (nt - t_lo + KS - 1) / KS;
   const bf16_t* kbase = P.k + (long)b * T * P.k_stride + hk * D;
   const bf16_t* vbase = P.v + (long)b * T * P.v_stride + hk * D;
   const uint32_t* mbase = DROP ? P.mask + (long)bh * nT * 2 * T : nullptr;   // wave-uniform
@@ -335,7 +344,7 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   GldsTile<D, kTile>::offsets(P.v_stride, wv, lane, voff);
   const uint32_t moff = (uint32_t)(mrow - mbase) * 4u;
   auto issue = [&](int it) {
-    const int t = it * KS + spu;
+    const int t = t_lo + it * KS + spu;
     if (it >= nit || t >= nt) return;
     char* st = smem + ((it % NST) * KS + spu) * SB;
     GldsTile<D, kTile>::load_sv(kbase + (long)t * kTile * P.k_stride, koff, st, wv);
@@ -386,6 +395,13 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
         for (int i = 0; i < 16; ++i)
           if (kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h > qi) sacc[n][i] = -INFINITY;
     }
+    if (WIN && kv0 <= q0 + 31 - W) {           // lower-edge tile: mask keys <= query - W
+#pragma unroll
+      for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h <= qi - W) sacc[n][i] = -INFINITY;
+    }
   };
   auto row_max = [&]() {                       // this tile's row max minus m
     float mx = sacc[0][0];
@@ -413,12 +429,35 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
     mv = splat16(-m);
     fresh = false;
   };
+  // With a window the invariant above does not hold: a lower-edge tile is fully masked for the later rows of
+  // the wave (mx = -inf), and a key split may see no tile of a row at all.  m stays -inf while a row has seen
+  // no key (its S chain then starts from 0, not from +inf); the row's first key sets m = mx, later tiles move
+  // it by mx when mx > kRescaleLog2.  A row that does not move has d = 0 (alpha = 1): every row's arithmetic
+  // depends on its own scores only, and a row without a visible key in the tile leaves m, l, O untouched
+  // (p = exp2(-inf) = 0).
+  auto rescale_win = [&](float mx) {
+    const bool empty = m == -INFINITY;
+    const bool moves = empty ? mx > -INFINITY : mx > kRescaleLog2;
+    const float d = moves ? mx : 0.f;
+    const float alpha = empty ? 1.f : __builtin_amdgcn_exp2f(-d);
+    l *= alpha;
+#pragma unroll
+    for (int dt = 0; dt < NACC; ++dt) oacc[dt] *= alpha;
+    m = moves ? (empty ? mx : m + d) : m;
+#pragma unroll
+    for (int n = 0; n < 2; ++n) sacc[n] -= d;
+    mv = splat16(m == -INFINITY ? 0.f : -m);
+  };
   auto softmax = [&]() {
     // lazy rescale: m moves only on the first tile or when a row max exceeds it by more than
     // kRescaleLog2 (p <= 2^8 in between); wave-uniform, rare after the first tiles
     {
       const float mx = row_max();
-      if (fresh || __ballot(mx > kRescaleLog2)) rescale(mx);
+      if constexpr (WIN) {
+        if (__ballot(m == -INFINITY ? mx > -INFINITY : mx > kRescaleLog2)) rescale_win(mx);
+      } else {
+        if (fresh || __ballot(mx > kRescaleLog2)) rescale(mx);
+      }
     }
     float ls0 = 0.f, ls1 = 0.f;
     static_for<32>([&](auto J) {
@@ -448,14 +487,16 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   auto mask_word = [&](const char* st) {
     return DROP ? *reinterpret_cast<const uint32_t*>(st + 2 * TB + wv * 256 + lane * 4) : 0u;
   };
-  auto visible = [&](int t) { return t < nt && (!CAUSAL || t * kTile <= q0 + 31); };
+  auto visible = [&](int t) {    // some row of the wave sees a key of tile t (WIN: its last key > q0 - W)
+    return t < nt && (!CAUSAL || t * kTile <= q0 + 31) && (!WIN || t * kTile + kTile - 1 > q0 - W);
+  };
 
   {
     for (int it = 0; it < nit; ++it) {
-      const int t = it * KS + spu;                   // wave-uniform: the tile branches are scalar
+      const int t = t_lo + it * KS + spu;            // wave-uniform: the tile branches are scalar
       // stages it+1 .. it+NST-2 (issued only if their tiles exist for this split) may stay in flight
       static_assert(NST <= 4, "the counted wait below assumes at most two later stages in flight");
-      const int later = NST < 3 ? 0 : min(NST - 2, min(nit - 1, (nt - 1 - spu) / KS) - it);
+      const int later = NST < 3 ? 0 : min(NST - 2, min(nit - 1, (nt - t_lo - 1 - spu) / KS) - it);
       if (NST > 3 && later >= 2) wait_vm<(NST > 3 ? 2 * GL : 0)>();
       else if (NST > 2 && later >= 1) wait_vm<(NST > 2 ? GL : 0)>();
       else wait_vm<0>();
@@ -491,7 +532,9 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
       const float* red = red0 + o * 4 * NF * 64;
       const float m1 = red[0], l1 = red[64];
       const float mn = fmaxf(m, m1);
-      const float a0 = __builtin_amdgcn_exp2f(m - mn), a1 = __builtin_amdgcn_exp2f(m1 - mn);
+      // WIN: a split that saw no key of the row (m = -inf, l = 0, O = 0) merges with weight zero
+      const float a0 = WIN && m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mn);
+      const float a1 = WIN && m1 == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m1 - mn);
       m = mn;
       l = l * a0 + l1 * a1;
 #pragma unroll
@@ -616,8 +659,9 @@ DLTB_DEV void dkdv_finish(const AttnArgs& P, char* smem, f32x16 (&dk)[D / 32], f
   store_acc_rows<D>(dvrow, dv, s_drop, h);
 }
 
-template <int D, bool CAUSAL, bool DROP, int KS>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false>
 __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
+  static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
   constexpr int TB = kTile * D * 2;
   constexpr int SB = dkdv_stage_bytes<D>();   // Q tile, dO tile, lse2[64], delta'[64], mask[64][4]
   constexpr int NACC = D / 32;
@@ -673,7 +717,11 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
   for (int dt = 0; dt < NACC; ++dt) { dk[dt] = f32x16{}; dv[dt] = f32x16{}; }
 
   const int t_begin = CAUSAL ? kblk0 / kTile : 0;
-  const int nit = (nT - t_begin + KS - 1) / KS;   // iterations per head
+  // sliding window W: key j is seen by queries j <= q < j + W, so the block's last key ends at query tile
+  // t_end - 1
+  const int W = WIN ? P.window : 0;
+  const int t_end = WIN ? min(nT, (kblk0 + kBlockRows - 1 + W - 1) / kTile + 1) : nT;
+  const int nit = (t_end - t_begin + KS - 1) / KS;   // iterations per head
   const int njobs = G * nit;
 
   const int wv = __builtin_amdgcn_readfirstlane(kw);
@@ -692,7 +740,7 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
   auto load = [&](int j) {
     int g, t;
     tile_of(j, g, t);
-    if (t >= nT) return;
+    if (t >= t_end) return;
     const int hq = hk * G * gsplit + g;
     const long bq = (long)b * P.Hq + hq;
     // Q / dO tiles straight into the stage buffer by LDS-DMA (it is not being read: the previous
@@ -711,7 +759,7 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
   auto store = [&](int j) {
     int g, t;
     tile_of(j, g, t);
-    if (t >= nT) return;
+    if (t >= t_end) return;
     char* base = smem + ((j & 1) * KS + sp) * SB;
     float* f = reinterpret_cast<float*>(base + 2 * TB);
     if (stid < kTile) {
@@ -768,7 +816,8 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
         }
       }
     };
-    auto softmax = [&](int mm, const f32x16& sa, const f32x16& dp, bool diag, f32x16& pd, f32x16& ds) {
+    auto softmax = [&](int mm, const f32x16& sa, const f32x16& dp, bool diag, bool ledge, f32x16& pd,
+                       f32x16& ds) {
       const int qb = t * kTile + 32 * mm;
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
@@ -786,6 +835,7 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
           const int i = 4 * g4 + e;
           float p = __builtin_amdgcn_exp2f(sa[i]);
           if (CAUSAL && diag && key > qb + 8 * g4 + 4 * h + e) p = 0.f;
+          if (WIN && ledge && qb + 8 * g4 + 4 * h + e >= key + W) p = 0.f;
           if (DROP) {     // dS = fma(p keep, dP', p D): the masked probability carries the keep bit
             const float pdv = __uint_as_float(__float_as_uint(p) & keep_mask_v(Mv[e], jbit));
             pd[i] = pdv;
@@ -809,25 +859,26 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
         }
       }
     };
-    if (t < nT) {
-      if (D == 128 && (!CAUSAL || t * kTile >= k0 + 31)) {
+    if (t < t_end) {
+      if (D == 128 && (!CAUSAL || t * kTile >= k0 + 31) && (!WIN || t * kTile + kTile - 1 < k0 + W)) {
         // full tile (no mask): both sub-tiles' S/dP first, so the second pair's MFMAs overlap the
         // first sub-tile's softmax, and its dV/dK MFMAs overlap the second softmax
         f32x16 sa0, dp0, sa1, dp1, pd, ds;
         sdp(0, sa0, dp0);
         sdp(1, sa1, dp1);
-        softmax(0, sa0, dp0, false, pd, ds);
+        softmax(0, sa0, dp0, false, false, pd, ds);
         accum(0, pd, ds);
-        softmax(1, sa1, dp1, false, pd, ds);
+        softmax(1, sa1, dp1, false, false, pd, ds);
         accum(1, pd, ds);
       } else {
 #pragma unroll
         for (int mm = 0; mm < 2; ++mm) {
           const int qb = t * kTile + 32 * mm;
           if (CAUSAL && qb + 31 < k0) continue;   // every query < every key of this wave
+          if (WIN && qb >= k0 + 31 + W) continue;  // every query >= every key + W
           f32x16 sa, dp, pd, ds;
           sdp(mm, sa, dp);
-          softmax(mm, sa, dp, qb < k0 + 31, pd, ds);
+          softmax(mm, sa, dp, qb < k0 + 31, WIN && qb + 31 >= k0 + W, pd, ds);
           accum(mm, pd, ds);
         }
       }
@@ -887,8 +938,9 @@ constexpr int dq_smem_bytes() {
   return ring > merge ? ring : merge;
 }
 
-template <int D, bool CAUSAL, bool DROP, int KS>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false>
 __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
+  static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
   constexpr int TB = kTile * D * 2;
   constexpr int NACC = D / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -948,7 +1000,9 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   const uint32_t* mbase = DROP ? P.mask + (long)bq * nT * 2 * T : nullptr;   // wave-uniform
   const uint32_t* mrow = DROP ? mbase + (long)h * T + qi : nullptr;
   const int nt = CAUSAL ? min(nT, (qb * kBlockRows + kBlockRows - 1) / kTile + 1) : nT;
-  const int nit = (nt + KS - 1) / KS;
+  const int W = WIN ? P.window : 0;              // the forward's tile range: t_lo .. nt - 1
+  const int t_lo = WIN ? max(0, qb * kBlockRows - W + 1) / kTile : 0;
+  const int nit = (nt - t_lo + KS - 1) / KS;
   const bf16_t* kbase = P.k + (long)b * T * P.k_stride + hk * D;
   const bf16_t* vbase = P.v + (long)b * T * P.v_stride + hk * D;
 
@@ -967,7 +1021,7 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   const uint32_t moff = (uint32_t)(mrow - mbase) * 4u;
   const int spu = __builtin_amdgcn_readfirstlane(sp);      // the key split is wave-uniform
   auto issue = [&](int it) {
-    const int t = it * KS + spu;
+    const int t = t_lo + it * KS + spu;
     if (it >= nit || t >= nt) return;
     char* st = smem + ((it % NST) * KS + spu) * SB;
     GldsTile<D, kTile>::load_sv(kbase + (long)t * kTile * P.k_stride, koff, st, wv);
@@ -983,9 +1037,9 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   for (int dt = 0; dt < NACC; ++dt) dq[dt] = f32x16{};
 
   for (int it = 0; it < nit; ++it) {
-    const int t = it * KS + sp;
+    const int t = t_lo + it * KS + sp;
     static_assert(NST <= 3, "the counted wait below assumes at most one later stage in flight");
-    if (NST > 2 && it + 1 < nit && (it + 1) * KS + sp < nt) wait_vm<(NST > 2 ? GL : 0)>();
+    if (NST > 2 && it + 1 < nit && t_lo + (it + 1) * KS + sp < nt) wait_vm<(NST > 2 ? GL : 0)>();
     else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     issue(it + NST - 1);                         // refills the buffer read in iteration it - 1
@@ -1006,11 +1060,13 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
     // softmax / dS of sub-tile n and dQ^T += K^T dS^T
     auto fin = [&](int n, const f32x16& sa, const f32x16& dp) {
       const bool diag = CAUSAL && kv0 + 32 * n + 31 > q0;
+      const bool ledge = WIN && kv0 + 32 * n <= q0 + 31 - W;     // some key <= some query - W
       f32x16 ds;
       static_for<16>([&](auto I) {
         constexpr int i = I;
         float p = __builtin_amdgcn_exp2f(sa[i]);
         if (diag && kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h > qi) p = 0.f;
+        if (ledge && kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h <= qi - W) p = 0.f;
         const float dpv = DROP ? (n == 0 ? keep_sel<mask_bit(0, i)>(dp[i], nd, mw)
                                          : keep_sel<mask_bit(1, i)>(dp[i], nd, mw)) : dp[i];
         ds[i] = p * dpv;
@@ -1028,6 +1084,7 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
           if (CAUSAL && kv0 + 32 * n > q0 + 31) continue;
+          if (WIN && kv0 + 32 * n + 31 <= q0 - W) continue;      // every key <= every query - W
           f32x16 sa, dp;
           sdp(n, sa, dp);
           fin(n, sa, dp);
@@ -1092,25 +1149,26 @@ long dltb_attn_mask_words(int B, int Hq, int T) { return (long)B * Hq * (T / kTi
 
 namespace {
 
-template <int D, bool C, bool DR>
+// WIN = true: the sliding-window instantiations (causal only), with the key splits of the causal kernels
+template <int D, bool C, bool DR, bool WIN = false>
 void set_attrs() {
-  (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, C, DR, fwd_ks<D, C>()>,
+  (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, C, DR, fwd_ks<D, C>(), WIN>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, fwd_smem_bytes<D, fwd_ks<D, C>()>());
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, C, DR, dq_ks<D, C>()>,
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, C, DR, dq_ks<D, C>(), WIN>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, dq_smem_bytes<D, dq_ks<D, C>()>());
-  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > dq_ks<D, C>())
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, C, DR, DLTB_DQ_KS64>,
+  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > dq_ks<D, C>() && !(WIN && DR))
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, C, DR, DLTB_DQ_KS64, WIN>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, dq_smem_bytes<D, DLTB_DQ_KS64>());
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<D, C, DR, dkdv_ks<D>()>,
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<D, C, DR, dkdv_ks<D>(), WIN>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, dkdv_smem_bytes<D>());
 }
 
-template <int D, bool C, bool DR>
+template <int D, bool C, bool DR, bool WIN = false>
 void launch_fwd(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = fwd_ks<D, C>();
   constexpr int smem = fwd_smem_bytes<D, KS>();
   dim3 grid((a.T / kBlockRows) * a.B * a.Hq);
-  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS>), grid, dim3(256 * KS), smem, st, a);
+  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS, WIN>), grid, dim3(256 * KS), smem, st, a);
 }
 
 #define DLTB_ATTN_DISPATCH(FN, D, C, DR, ...)           \
@@ -1123,6 +1181,17 @@ void launch_fwd(const AttnArgs& a, hipStream_t st) {
       else   { if (DR) FN<128, false, true>(__VA_ARGS__); else FN<128, false, false>(__VA_ARGS__); } \
     }                                                   \
   } while (0)
+
+// the sliding-window (causal) instantiations
+#define DLTB_ATTN_DISPATCH_WIN(FN, D, DR, ...)          \
+  do {                                                  \
+    if (D == 64) { if (DR) FN<64, true, true, true>(__VA_ARGS__); else FN<64, true, false, true>(__VA_ARGS__); } \
+    else         { if (DR) FN<128, true, true, true>(__VA_ARGS__); else FN<128, true, false, true>(__VA_ARGS__); } \
+  } while (0)
+
+// A window of T or more keys is plain causal attention and runs the causal kernels (bitwise the same result);
+// only 0 < window < T takes the WIN instantiations.
+bool windowed(int causal, int window, int T) { return causal && window > 0 && window < T; }
 
 }  // namespace
 
@@ -1138,6 +1207,10 @@ void dltb_attn_init_attributes() {
   set_attrs<128, false, true>();
   set_attrs<128, true, false>();
   set_attrs<128, true, true>();
+  set_attrs<64, true, false, true>();
+  set_attrs<64, true, true, true>();
+  set_attrs<128, true, false, true>();
+  set_attrs<128, true, true, true>();
 }
 
 void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const int64_t* seed,
@@ -1149,13 +1222,18 @@ void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const 
 void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
-                   hipStream_t st) {
+                   hipStream_t st, int window) {
   AttnArgs a = make_args(q, k, v, qs, ks, vs, B, T, Hq, Hkv, scale, causal, thr16, drop_scale,
                          nullptr, 0);
   a.out = (bf16_t*)o;
   a.out_stride = os;
   a.lse = lse;
   a.mask = mask;
+  if (windowed(causal, window, T)) {
+    a.window = window;
+    DLTB_ATTN_DISPATCH_WIN(launch_fwd, D, thr16 != 0, a, st);
+    return;
+  }
   DLTB_ATTN_DISPATCH(launch_fwd, D, causal != 0, thr16 != 0, a, st);
 }
 
@@ -1178,11 +1256,11 @@ void dltb_attn_bwd_delta(const void* o, const void* dout, float* delta, long os,
 }
 
 namespace {
-template <int D, bool C, bool DR>
+template <int D, bool C, bool DR, bool WIN = false>
 void launch_dkdv(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = dkdv_ks<D>();
 
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, C, DR, KS>), dim3((a.T / kBlockRows) * a.B * a.Hkv * a.gsplit),
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, C, DR, KS, WIN>), dim3((a.T / kBlockRows) * a.B * a.Hkv * a.gsplit),
                      dim3(256 * KS), dkdv_smem_bytes<D>(), st, a);
   if (a.gsplit > 1) {
     const long rows = (long)a.B * a.T;
@@ -1191,22 +1269,24 @@ void launch_dkdv(const AttnArgs& a, hipStream_t st) {
                        a.part, a.gsplit, rows, cols, a.out, a.out_stride, a.out2, a.out2_stride);
   }
 }
-template <int D, bool C, bool DR, int KS>
+template <int D, bool C, bool DR, int KS, bool WIN>
 void launch_dq_ks(const AttnArgs& a, hipStream_t st) {
   constexpr int smem = dq_smem_bytes<D, KS>();
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, C, DR, KS>), dim3((a.T / kBlockRows) * a.B * a.Hq), dim3(256 * KS),
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, C, DR, KS, WIN>), dim3((a.T / kBlockRows) * a.B * a.Hq), dim3(256 * KS),
                      smem, st, a);
 }
 // Causal D = 64 dQ: 2 key splits short, 3 from T = 1024 (A/B, profiles/attention_causal_d64_ks_r5.txt: T 2048
 // 35.4 -> 32.4 us with 3; B4 T512 12.6 with 2 against 13.1)
+// The windowed kernel with dropout stays at 2 for every T: at 3 it needs 24 B of scratch per lane
+// (profiles/attention_window_resources.txt), and no windowed instantiation may spill.
 constexpr int kDqCausalLongT = 1024;
-template <int D, bool C, bool DR>
+template <int D, bool C, bool DR, bool WIN = false>
 void launch_dq(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = dq_ks<D, C>();
-  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > KS) {
-    if (a.T >= kDqCausalLongT) return launch_dq_ks<D, C, DR, DLTB_DQ_KS64>(a, st);
+  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > KS && !(WIN && DR)) {
+    if (a.T >= kDqCausalLongT) return launch_dq_ks<D, C, DR, DLTB_DQ_KS64, WIN>(a, st);
   }
-  launch_dq_ks<D, C, DR, KS>(a, st);
+  launch_dq_ks<D, C, DR, KS, WIN>(a, st);
 }
 }  // namespace
 
@@ -1216,7 +1296,17 @@ void launch_dq(const AttnArgs& a, hipStream_t st) {
 // step waits for the heaviest workgroup.  Splitting the G query heads of each KV group over
 // several workgroups (fp32 partials + one reduce) makes the grid several waves deep, dispatched
 // heaviest first.  DLTB_DKDV_GSPLIT = n forces n (1 = off).
-int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal) {
+//
+// With a sliding window (0 < window < T) the grid is balanced: every key block sweeps at most window / 64 + 3
+// query tiles per head, whatever T is, so the dispatch order (kept as the causal one) does not matter and
+// the split is only needed to fill the chip: double it until one workgroup per CU (256) exists, where the
+// causal rule asks for two rounds of unequal blocks.  The rule was reasoned from the per-block work and
+// then checked against forced splits at the Mistral-7B head shape (profiles/attention_window.txt): it picks
+// the fastest split at T 4096 / W 1024 (256 workgroups: 1 -> 173.9 us, 2 -> 191.8, 4 -> 214.8) and at
+// T 2048 / W 512 (128 workgroups: 2 -> 66.8 us, 1 -> 100.6, 4 -> 81.7).  At T 8192 / W 4096, where half of
+// the key blocks still sweep a causal triangle, it leaves the grid unsplit (1172 us) although 2 measured
+// 974 us; the dispatch order of the unsplit grid and a work-based rule for W near T are not measured.
+int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal, int window) {
   const int G = Hq / Hkv;
   if (!causal || G < 2) return 1;
   static const int forced = [] {
@@ -1225,8 +1315,9 @@ int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal) {
   }();
   if (forced > 0) return G % forced == 0 ? forced : 1;
   const long wgs = (long)(T / kBlockRows) * B * Hkv;
+  const long target = windowed(causal, window, T) ? 256 : 2L * 256;
   int s = 1;
-  while (s < G && wgs * s < 2L * 256 && G % (2 * s) == 0) s *= 2;
+  while (s < G && wgs * s < target && G % (2 * s) == 0) s *= 2;
   return s;
 }
 
@@ -1236,7 +1327,7 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
                         void* out2, long qs, long ks, long vs, long dos, long outs, long out2s,
                         int B, int T, int Hq, int Hkv, int D, float scale, int causal,
                         uint32_t thr16, float drop_scale, hipStream_t st, const void* o, long os,
-                        int gsplit, float* part_buf) {
+                        int gsplit, float* part_buf, int window) {
   AttnArgs a = make_args(q, k, v, qs, ks, vs, B, T, Hq, Hkv, scale, causal, thr16, drop_scale,
                          nullptr, 0);
   if (part == 0 && gsplit > 1 && part_buf && (Hq / Hkv) % gsplit == 0) {
@@ -1254,6 +1345,14 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
   a.out2_stride = out2s;
   a.o = part == 1 ? (const bf16_t*)o : nullptr;     // dQ pass computes and writes delta itself
   a.o_stride = os;
+  if (windowed(causal, window, T)) {
+    a.window = window;
+    if (part == 0)
+      DLTB_ATTN_DISPATCH_WIN(launch_dkdv, D, thr16 != 0, a, st);
+    else
+      DLTB_ATTN_DISPATCH_WIN(launch_dq, D, thr16 != 0, a, st);
+    return;
+  }
   if (part == 0)
     DLTB_ATTN_DISPATCH(launch_dkdv, D, causal != 0, thr16 != 0, a, st);
   else

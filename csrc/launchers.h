@@ -103,7 +103,7 @@ void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const 
 void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
-                   hipStream_t st);
+                   hipStream_t st, int window = 0);
 void dltb_attn_bwd_delta(const void* o, const void* dout, float* delta, long os, long dos, int B,
                          int T, int Hq, int D, hipStream_t st);
 void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, const void* dout,
@@ -111,9 +111,9 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
                         void* out2, long qs, long ks, long vs, long dos, long outs, long out2s,
                         int B, int T, int Hq, int Hkv, int D, float scale, int causal,
                         uint32_t thr16, float drop_scale, hipStream_t st, const void* o = nullptr,
-                        long os = 0, int gsplit = 1, float* part_buf = nullptr);
+                        long os = 0, int gsplit = 1, float* part_buf = nullptr, int window = 0);
 // dK/dV workgroups per KV head for a causal GQA backward (1 = one workgroup sums the whole group)
-int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal);
+int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal, int window = 0);
 void dltb_attn_init_attributes();
 
 // ---- batched column reductions (colreduce.hip)

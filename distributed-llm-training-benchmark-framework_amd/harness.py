@@ -57,6 +57,9 @@ def build_parser():
     # model & data
     p.add_argument("--tier", type=str, required=True, choices=["A", "B", "default", "M7B", "M7B_narrow", "tiny", "mtiny"])
     p.add_argument("--seq-len", type=int, required=True)
+    p.add_argument("--sliding-window", type=int, default=None, metavar="N",
+                   help="causal tiers (M7B, M7B_narrow, mtiny): query i attends to keys i - N < j <= i (N keys "
+                        "including its own, the Mistral mask); default: no window")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -186,6 +189,9 @@ def train(args):
         mcfg = get_model_config(args.tier, args.seq_len)
         if args.dropout is not None:
             mcfg.dropout = args.dropout
+        if getattr(args, "sliding_window", None) is not None:
+            mcfg.sliding_window = args.sliding_window
+            mcfg.validate()
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         n_params = model.num_params()
@@ -358,7 +364,13 @@ def train(args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.sliding_window is not None:
+        if args.sliding_window < 1:
+            parser.error("--sliding-window must be >= 1")
+        if not get_model_config(args.tier, args.seq_len).causal:
+            parser.error(f"--sliding-window needs a causal tier; tier {args.tier} attends non-causally")
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:
         args.deepspeed_config = default_config_path(args.strategy)
         print(f"[dltb] --deepspeed-config not given; using {args.deepspeed_config}", flush=True)

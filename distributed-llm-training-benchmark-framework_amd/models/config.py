@@ -34,6 +34,20 @@ class ModelConfig:
     causal: bool = False             # TinyGPT reproduces the reference's NON-causal MHA
     tie_embeddings: bool = True
     tier: str = "custom"
+    # causal sliding window W: query i sees keys i - W < j <= i (W keys including its own); None = no window
+    sliding_window: Optional[int] = None
+
+    def __post_init__(self):
+        self.validate()
+
+    def validate(self):
+        """Raises ValueError for an inconsistent config (also called again where a field is set later)."""
+        w = self.sliding_window
+        if w is not None:
+            if isinstance(w, bool) or not isinstance(w, int) or w < 1:
+                raise ValueError(f"sliding_window must be an integer >= 1 or None, got {w!r}")
+            if not self.causal:
+                raise ValueError("sliding_window needs causal=True")
 
     @property
     def head_dim(self) -> int:
@@ -64,7 +78,8 @@ class ModelConfig:
         return V * d + L * per_block + d + head
 
     def train_flops_per_token(self, seq_len: int) -> float:
-        """6 * N_matmul + attention (12 * L * T * d non-causal, halved when causal)."""
+        """6 * N_matmul + attention (12 * L * T * d non-causal, halved when causal; with a sliding window
+        W < T a row sees (W (T - W) + W^2 / 2) / T keys on average instead of T / 2)."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d
@@ -72,6 +87,9 @@ class ModelConfig:
             kvd = self.kv_heads * self.head_dim
             n_mat = L * (2 * d * d + 2 * kvd * d + 3 * d * self.ffn_dim) + self.vocab_size * d
         attn = 12 * L * seq_len * d * (0.5 if self.causal else 1.0)
+        w = self.sliding_window
+        if self.causal and w is not None and w < seq_len:
+            attn = 12 * L * d * (w * (seq_len - w) + w * w / 2.0) / seq_len
         return 6.0 * n_mat + attn
 
 

@@ -101,7 +101,7 @@ class _LayerFn(torch.autograd.Function):
         F_.rope_(qkv, cos, sin, T, Hq + Hkv, D, False)
         qd, kd = Hq * D, Hkv * D
         o, lse, aux = F_.attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
-                                  1.0 / math.sqrt(D), True, 0.0, rt.seed, 0)
+                                  1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=cfg.sliding_window or 0)
         a = F_.linear_fwd(o, wo)
         x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
         gu = F_.linear_fwd(h2, wgu)
@@ -140,7 +140,7 @@ class _LayerFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                     dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
-                    1.0 / math.sqrt(D), True, 0.0, rt.seed, 0)
+                    1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=cfg.sliding_window or 0)
         F_.rope_(dqkv, cos, sin, T, Hq + Hkv, D, True)      # RoPE is orthogonal: grad = R(-theta) g
         F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
         dh1 = F_.linear_dgrad(dqkv, wqkv, rt.weight_t(unit, 1, wqkv))

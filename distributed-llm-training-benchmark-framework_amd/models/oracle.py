@@ -113,7 +113,12 @@ class OracleMistral(nn.Module):
             q, k = _rope(q, cos, sin), _rope(k, cos, sin)
             k = k.repeat_interleave(H // Hkv, 1)
             v = v.repeat_interleave(H // Hkv, 1)
-            o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+            if cfg.sliding_window:      # band mask: query i sees keys i - W < j <= i
+                i = torch.arange(T, device=idx.device)
+                band = (i[None, :] <= i[:, None]) & (i[None, :] > i[:, None] - cfg.sliding_window)
+                o = F.scaled_dot_product_attention(q, k, v, attn_mask=band)
+            else:
+                o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
             x = x + layer.self_attn.o_proj(o.transpose(1, 2).reshape(B, T, H * hd))
             gu = layer.mlp.gate_up_proj(layer.post_attention_layernorm(x))
             g, u = gu.chunk(2, -1)

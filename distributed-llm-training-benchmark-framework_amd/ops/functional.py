@@ -474,28 +474,32 @@ def attn_mask(B, T, Hq, p, seed, site, like):
     return ext().attn_mask(B, T, Hq, p, seed.device_tensor, site, like)
 
 
-def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, mask=None, o_out=None):
-    """Returns (o, lse, aux); ``aux`` (the packed dropout mask on the GPU) goes back into attn_bwd."""
+def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, mask=None, o_out=None, window=0):
+    """Returns (o, lse, aux); ``aux`` (the packed dropout mask on the GPU) goes back into attn_bwd.
+    ``window`` = W > 0 (causal only): query i sees keys ``i - W < j <= i``; 0 = no window."""
+    ref.check_window(window, causal)
     if _gpu(q):
         if p > 0 and mask is None:
             mask = ext().attn_mask(B, T, Hq, p, seed.device_tensor, site, q)
-        o, lse = ext().attn_fwd(q, k, v, mask if p > 0 else None, B, T, Hq, Hkv, scale, causal, p, o_out)
+        o, lse = ext().attn_fwd(q, k, v, mask if p > 0 else None, B, T, Hq, Hkv, scale, causal, p, o_out,
+                                window)
         return o, lse, (mask if p > 0 else None)
-    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site)
+    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window)
     return _into(o_out, o), lse, None
 
 
-def attn_bwd(q, k, v, o, do, lse, aux, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site):
+def attn_bwd(q, k, v, o, do, lse, aux, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0):
     """dQ (query-major kernel, which also forms delta = rowsum(dO * O) for its rows), then dK/dV
-    (key-major kernel, reading that delta)."""
+    (key-major kernel, reading that delta).  ``window``: as in :func:`attn_fwd`."""
+    ref.check_window(window, causal)
     if _gpu(q):
         C = ext()
         m = aux if p > 0 else None
         delta = torch.empty_like(lse)
-        C.attn_bwd_part(1, q, k, v, do, lse, delta, m, dq, None, B, T, Hq, Hkv, scale, causal, p, o)
-        C.attn_bwd_part(0, q, k, v, do, lse, delta, m, dk, dv, B, T, Hq, Hkv, scale, causal, p)
+        C.attn_bwd_part(1, q, k, v, do, lse, delta, m, dq, None, B, T, Hq, Hkv, scale, causal, p, o, window)
+        C.attn_bwd_part(0, q, k, v, do, lse, delta, m, dk, dv, B, T, Hq, Hkv, scale, causal, p, None, window)
     else:
-        ref.attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site)
+        ref.attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window)
 
 
 # ------------------------------------------------------------------------------ linear

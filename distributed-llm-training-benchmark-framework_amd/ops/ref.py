@@ -187,7 +187,17 @@ def xent_fwd_bwd_(logits, targets, ignore_index):
 
 
 # ------------------------------------------------------------------------------ attention
-def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal):
+def check_window(window, causal):
+    """Sliding window ``W >= 1``: query i sees key j iff ``i - W < j <= i`` (W keys including its own, the
+    Hugging Face Mistral mask); 0 = no window.  Only defined together with the causal mask."""
+    if window < 0:
+        raise ValueError(f"attention: window must be >= 0 (0 = no window), got {window}")
+    if window > 0 and not causal:
+        raise ValueError("attention: a sliding window needs causal=True")
+
+
+def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0):
+    check_window(window, causal)
     qh = _f(q).reshape(B, T, Hq, D).transpose(1, 2)              # [B,Hq,T,D]
     kh = _f(k).reshape(B, T, Hkv, D).transpose(1, 2)
     if Hq != Hkv:
@@ -195,6 +205,8 @@ def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal):
     s = torch.matmul(qh, kh.transpose(-1, -2)) * scale
     if causal:
         m = torch.ones(T, T, dtype=torch.bool, device=q.device).triu(1)
+        if 0 < window < T:                                            # keys j <= i - W are out of the band
+            m |= torch.ones(T, T, dtype=torch.bool, device=q.device).tril(-window)
         s = s.masked_fill(m, float("-inf"))
     return s
 
@@ -208,9 +220,9 @@ def _attn_keep(B, Hq, T, p, seed, site, device):
     return attn_keep_mask(s, rows, cols, p).view(B, Hq, T, T)
 
 
-def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site):
+def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0):
     D = q.shape[1] // Hq
-    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal)
+    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window)
     lse = torch.logsumexp(s, -1)                                      # [B,Hq,T]
     pr = torch.exp(s - lse[..., None])
     keep = _attn_keep(B, Hq, T, p, seed, site, q.device)
@@ -223,13 +235,13 @@ def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site):
     return o.to(q.dtype), _f(lse).contiguous()
 
 
-def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site):
+def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0):
     D = q.shape[1] // Hq
     G = Hq // Hkv
-    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal)
+    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window)
     pr = torch.exp(s - lse.view(B, Hq, T)[..., None])
     keep = _attn_keep(B, Hq, T, p, seed, site, q.device)
-    z = torch.ones_like(pr) if keep is None else _f(keep) / (1.0 - p)
+    z = torch.ones_like(pr) if keep is None else keep.to(pr.dtype) / (1.0 - p)   # fp64 inputs stay fp64
     qh = _f(q).reshape(B, T, Hq, D).transpose(1, 2)
     kh = _f(k).reshape(B, T, Hkv, D).transpose(1, 2).repeat_interleave(G, dim=1)
     vh = _f(v).reshape(B, T, Hkv, D).transpose(1, 2).repeat_interleave(G, dim=1)

@@ -2,10 +2,17 @@
 """Attention kernel microbenchmark (forward, dK/dV, dQ, dropout-mask) on the two model shapes.
 
     python scripts/bench_attn.py [--iters 50]
+    python scripts/bench_attn.py --window 4096 --seq-lens 8192,16384,32768   # sliding window vs full causal
 
 Prints one line per kernel: time per call and TFLOP/s (causal FLOPs counted over the visible
 half).  Shapes: TinyGPT-A (B1 T2048 H16 D64, dropout 0.1, non-causal) and Mistral-7B
 (B1 T4096 Hq32 Hkv8 D128, causal).
+
+``--window W`` times forward, dQ and dK/dV of the Mistral-7B attention shape at each ``--seq-lens`` length
+with the window (query i sees keys i - W < j <= i) and without it, in one process: the two variants
+alternate over ``--rounds`` rounds of ``--iters`` calls (after a warm-up round), and the median round is
+reported with the min .. max spread, next to the ratio of visited 64-key tiles (window / causal) that the
+kernels' tile bounds give.
 """
 import argparse
 import json
@@ -76,13 +83,74 @@ def run(name, B, T, Hq, Hkv, D, causal, p, iters):
     return {k: v[0] for k, v in res.items()}
 
 
+def tile_counts(T, W):
+    """64-key tiles the query-major kernels (forward, dQ) visit per (batch, head) and 64-query tiles the
+    key-major kernel (dK/dV) visits per (batch, KV head, query head), from the bounds of csrc/attention.hip
+    (128-row blocks); W = 0: full causal."""
+    qmaj = kmaj = 0
+    for blk in range(T // 128):
+        hi = min(T // 64, (blk * 128 + 127) // 64 + 1)
+        lo = max(0, blk * 128 - W + 1) // 64 if W else 0
+        qmaj += hi - lo
+        end = min(T // 64, (blk * 128 + 127 + W - 1) // 64 + 1) if W else T // 64
+        kmaj += end - blk * 128 // 64
+    return qmaj, kmaj
+
+
+def run_window(T, W, iters, rounds, B=1, Hq=32, Hkv=8, D=128, p=0.0):
+    C = ext()
+    g = torch.Generator(device="cuda").manual_seed(0)
+    dev = "cuda"
+    qkv = torch.randn(B * T, (Hq + 2 * Hkv) * D, device=dev, dtype=torch.bfloat16, generator=g)
+    q, k, v = qkv[:, :Hq * D], qkv[:, Hq * D:(Hq + Hkv) * D], qkv[:, (Hq + Hkv) * D:]
+    do = torch.randn(B * T, Hq * D, device=dev, dtype=torch.bfloat16, generator=g)
+    seed = torch.tensor([1234], device=dev, dtype=torch.int64)
+    scale = D ** -0.5
+    mask = C.attn_mask(B, T, Hq, p, seed, 1, q) if p > 0 else None
+    dq = torch.empty_like(q)
+    dkv = torch.empty(B * T, 2 * Hkv * D, device=dev, dtype=torch.bfloat16)
+    dk, dv = dkv[:, :Hkv * D], dkv[:, Hkv * D:]
+    fns = {}
+    for w in (0, W):
+        o, lse = C.attn_fwd(q, k, v, mask, B, T, Hq, Hkv, scale, True, p, window=w)
+        delta = C.attn_bwd_delta(o, do, B, T, Hq)
+        fns["fwd", w] = lambda w=w: C.attn_fwd(q, k, v, mask, B, T, Hq, Hkv, scale, True, p, window=w)
+        fns["dq", w] = lambda w=w, lse=lse, delta=delta: C.attn_bwd_part(
+            1, q, k, v, do, lse, delta, mask, dq, None, B, T, Hq, Hkv, scale, True, p, window=w)
+        fns["dkdv", w] = lambda w=w, lse=lse, delta=delta: C.attn_bwd_part(
+            0, q, k, v, do, lse, delta, mask, dk, dv, B, T, Hq, Hkv, scale, True, p, window=w)
+    times = {key: [] for key in fns}
+    for r in range(rounds + 1):                 # round 0 warms up; causal and windowed calls alternate
+        for key, fn in fns.items():
+            us = timeit(fn, iters)
+            if r:
+                times[key].append(us)
+    full, win = tile_counts(T, 0), tile_counts(T, W)
+    out = {}
+    for kname, tiles in (("fwd", win[0] / full[0]), ("dq", win[0] / full[0]), ("dkdv", win[1] / full[1])):
+        med = {w: sorted(times[kname, w])[len(times[kname, w]) // 2] for w in (0, W)}
+        spread = {w: (min(times[kname, w]), max(times[kname, w])) for w in (0, W)}
+        out[kname] = dict(causal_us=med[0], window_us=med[W], time_ratio=med[W] / med[0], tile_ratio=tiles)
+        print(f"T {T:6d} W {W:5d} {kname:5s} causal {med[0]:9.1f} us ({spread[0][0]:.1f} .. {spread[0][1]:.1f})  "
+              f"window {med[W]:9.1f} us ({spread[W][0]:.1f} .. {spread[W][1]:.1f})  "
+              f"time ratio {med[W] / med[0]:.3f}  tile ratio {tiles:.3f}", flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--shapes", default="tinygpt_a,m7b")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--window", type=int, default=0, help="compare this sliding window with full causal attention")
+    ap.add_argument("--seq-lens", default="8192,16384,32768", help="sequence lengths of the --window comparison")
+    ap.add_argument("--rounds", type=int, default=5, help="interleaved rounds of the --window comparison")
     a = ap.parse_args()
-    out = {n: run(n, iters=a.iters, **SHAPES[n]) for n in a.shapes.split(",")}
+    if a.window > 0:
+        out = {f"T{T}_W{a.window}": run_window(T, a.window, a.iters, a.rounds)
+               for T in (int(x) for x in a.seq_lens.split(","))}
+    else:
+        out = {n: run(n, iters=a.iters, **SHAPES[n]) for n in a.shapes.split(",")}
     if a.json:
         with open(a.json, "w") as f:
             json.dump(out, f, indent=1)
