@@ -89,6 +89,8 @@ struct AttnArgs {
   int gsplit;       // bwd_dkdv: workgroups per KV head, each summing G / gsplit query heads
   int window;       // WIN kernels: query i sees keys i - window < j <= i (0 < window < T; else unused)
   float* part;      // bwd_dkdv with gsplit > 1: fp32 partials [gsplit][2][B*T][Hkv*D] (scaled)
+  const int* bounds;   // DOC kernels: int32 [2][B][T], plane 0 = lo (first key query i sees), plane 1 = hi (one
+                       // past the last query that sees key j); both non-decreasing along T, lo[i] <= i < hi[i]
 };
 
 // accumulator registers 8s .. 8s+7 -> bf16 B operand of k-step s
@@ -169,6 +171,52 @@ __global__ __launch_bounds__(256) void attn_mask_kernel(uint32_t* __restrict__ m
   attn_mask_word(mask, T, thr16, seed_ptr, site, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
 }
 
+// =============================================================================== document bounds
+// Packed sequences: a token equal to eos ends a document and belongs to it.  For batch row b (one workgroup):
+//   lo[i] = 0 if no EOS in idx[b, :i], else 1 + the largest e < i with idx[b, e] == eos     (forward max-scan)
+//   hi[j] = T if no EOS in idx[b, j:], else 1 + the smallest e >= j with idx[b, e] == eos   (backward min-scan)
+// and with a sliding window W > 0 folded in lo[i] = max(lo[i], i - W + 1), hi[j] = min(hi[j], j + W).  Key j is
+// visible to query i iff lo[i] <= j <= i  <=>  j <= i < hi[j].  Both planes are non-decreasing and
+// lo[i] <= i < hi[i].  Each thread scans a contiguous chunk of the row, the 256 chunk results are scanned
+// through LDS, and a second pass over the chunk writes the planes: one launch, no host sync, any T >= 1.
+__global__ __launch_bounds__(256) void attn_doc_bounds_kernel(const int64_t* __restrict__ idx, int* __restrict__ bounds,
+                                                              int B, int T, int64_t eos, int window) {
+  __shared__ int last_s[256], first_s[256];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int chunk = (T + 255) / 256;
+  const int s = min(T, tid * chunk), e = min(T, s + chunk);
+  const int64_t* row = idx + (long)b * T;
+  int la = -1, fi = T - 1;        // last / first EOS of the chunk; T - 1 stands for "none" (hi = T either way)
+  for (int i = s; i < e; ++i)
+    if (row[i] == eos) {
+      la = i;
+      fi = min(fi, i);
+    }
+  last_s[tid] = la;
+  first_s[tid] = fi;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {      // inclusive max-scan forward, min-scan backward
+    const int a = tid >= off ? max(last_s[tid], last_s[tid - off]) : last_s[tid];
+    const int c = tid + off < 256 ? min(first_s[tid], first_s[tid + off]) : first_s[tid];
+    __syncthreads();
+    last_s[tid] = a;
+    first_s[tid] = c;
+    __syncthreads();
+  }
+  int* lo = bounds + (long)b * T;
+  int* hi = bounds + ((long)B + b) * T;
+  int run = tid > 0 ? last_s[tid - 1] : -1;      // last EOS before this chunk
+  for (int i = s; i < e; ++i) {
+    lo[i] = window > 0 ? max(run + 1, i - window + 1) : run + 1;
+    if (row[i] == eos) run = i;
+  }
+  run = tid < 255 ? first_s[tid + 1] : T - 1;    // first EOS after this chunk
+  for (int i = e - 1; i >= s; --i) {
+    if (row[i] == eos) run = i;
+    hi[i] = window > 0 ? min(run + 1, i + window) : run + 1;
+  }
+}
+
 // =============================================================================== forward
 // Workgroup = KS key-splits x 4 waves; wave (qw, sp) owns query rows q0 .. q0+31 and the key tiles
 // t == sp (mod KS).  KS = 2 doubles the waves per query block (2 waves / SIMD even at B*Hq*T/128
@@ -180,6 +228,14 @@ __global__ __launch_bounds__(256) void attn_mask_kernel(uint32_t* __restrict__ m
 // WIN (causal only, its own instantiations): a sliding window P.window = W, query i sees keys i - W < j <= i.
 // The key tiles start at t_lo instead of 0, tiles below a wave's band are skipped, lower-edge tiles mask keys
 // <= query - W, and the online softmax handles rows / key splits that have seen no key yet (rescale_win).
+// DOC (causal only, its own instantiations): per-row bounds P.bounds from attn_doc_bounds_kernel, the document
+// mask of packed sequences with the window already folded in: query i sees keys lo[i] <= j <= i.  lo is
+// non-decreasing, so the block's tiles start at lo[first row of the block] / 64, a wave skips the tiles below
+// lo[its first row], and a tile is a lower-edge tile while it starts below lo[the wave's last row].  Unlike the
+// window, one block can hold many edge tiles (documents shorter than a tile: every tile is one) and whole key
+// splits without a visible tile; the rows without a key in a tile take the windowed softmax's NaN-safe paths.
+// The kernels trust the bounds: they are not validated on the device (no sync), only the tile range is clamped
+// to the sequence, so hand-made bounds that are not monotone or break lo[i] <= i < hi[i] give wrong results.
 constexpr float kRescaleLog2 = 8.f;
 
 template <int I>
@@ -295,9 +351,11 @@ constexpr int fwd_stage_bytes() { return 2 * kTile * D * 2 + 1024; }   // K, V, 
 template <int D, int KS = fwd_ks<D>()>
 constexpr int fwd_smem_bytes() { return fwd_nst<D, KS>() * KS * fwd_stage_bytes<D>(); }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false>
 __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
+  constexpr bool BAND = WIN || DOC;     // rows / key splits may see no key of a visited tile
   constexpr int TB = kTile * D * 2;
   constexpr int NACC = D / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -322,7 +380,13 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   // sliding window W: row qi sees keys qi - W < key <= qi, so the block's first row starts at key tile t_lo;
   // the key splits are numbered from there (t = t_lo + it * KS + split)
   const int W = WIN ? P.window : 0;
-  const int t_lo = WIN ? max(0, qb * kBlockRows - W + 1) / kTile : 0;
+  // document bounds: this row's first key, and those of the wave's first / last row (lanes 0 / 31: wave-uniform)
+  const int lo_q = DOC ? P.bounds[(long)b * T + qi] : 0;
+  const int lo_w0 = DOC ? __builtin_amdgcn_readfirstlane(lo_q) : 0;
+  const int lo_w1 = DOC ? __builtin_amdgcn_readlane(lo_q, 31) : 0;
+  const int t_lo = WIN   ? max(0, qb * kBlockRows - W + 1) / kTile
+                   : DOC ? min(max(P.bounds[(long)b * T + qb * kBlockRows], 0), qb * kBlockRows) / kTile
+                         : 0;
   const int nit = (nt - t_lo + KS - 1) / KS;
   const bf16_t* kbase = P.k + (long)b * T * P.k_stride + hk * D;
   const bf16_t* vbase = P.v + (long)b * T * P.v_stride + hk * D;
@@ -402,6 +466,13 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
         for (int i = 0; i < 16; ++i)
           if (kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h <= qi - W) sacc[n][i] = -INFINITY;
     }
+    if (DOC && kv0 < lo_w1) {                  // lower-edge tile: mask keys < lo[query]
+#pragma unroll
+      for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h < lo_q) sacc[n][i] = -INFINITY;
+    }
   };
   auto row_max = [&]() {                       // this tile's row max minus m
     float mx = sacc[0][0];
@@ -453,7 +524,7 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
     // kRescaleLog2 (p <= 2^8 in between); wave-uniform, rare after the first tiles
     {
       const float mx = row_max();
-      if constexpr (WIN) {
+      if constexpr (BAND) {
         if (__ballot(m == -INFINITY ? mx > -INFINITY : mx > kRescaleLog2)) rescale_win(mx);
       } else {
         if (fresh || __ballot(mx > kRescaleLog2)) rescale(mx);
@@ -488,7 +559,8 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
     return DROP ? *reinterpret_cast<const uint32_t*>(st + 2 * TB + wv * 256 + lane * 4) : 0u;
   };
   auto visible = [&](int t) {    // some row of the wave sees a key of tile t (WIN: its last key > q0 - W)
-    return t < nt && (!CAUSAL || t * kTile <= q0 + 31) && (!WIN || t * kTile + kTile - 1 > q0 - W);
+    return t < nt && (!CAUSAL || t * kTile <= q0 + 31) && (!WIN || t * kTile + kTile - 1 > q0 - W) &&
+           (!DOC || t * kTile + kTile - 1 >= lo_w0);
   };
 
   {
@@ -532,9 +604,9 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
       const float* red = red0 + o * 4 * NF * 64;
       const float m1 = red[0], l1 = red[64];
       const float mn = fmaxf(m, m1);
-      // WIN: a split that saw no key of the row (m = -inf, l = 0, O = 0) merges with weight zero
-      const float a0 = WIN && m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mn);
-      const float a1 = WIN && m1 == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m1 - mn);
+      // WIN / DOC: a split that saw no key of the row (m = -inf, l = 0, O = 0) merges with weight zero
+      const float a0 = BAND && m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mn);
+      const float a1 = BAND && m1 == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m1 - mn);
       m = mn;
       l = l * a0 + l1 * a1;
 #pragma unroll
@@ -659,9 +731,10 @@ DLTB_DEV void dkdv_finish(const AttnArgs& P, char* smem, f32x16 (&dk)[D / 32], f
   store_acc_rows<D>(dvrow, dv, s_drop, h);
 }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false>
 __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
   constexpr int TB = kTile * D * 2;
   constexpr int SB = dkdv_stage_bytes<D>();   // Q tile, dO tile, lse2[64], delta'[64], mask[64][4]
   constexpr int NACC = D / 32;
@@ -720,7 +793,16 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
   // sliding window W: key j is seen by queries j <= q < j + W, so the block's last key ends at query tile
   // t_end - 1
   const int W = WIN ? P.window : 0;
-  const int t_end = WIN ? min(nT, (kblk0 + kBlockRows - 1 + W - 1) / kTile + 1) : nT;
+  // document bounds: key j is seen by queries j <= q < hi[j]; hi is non-decreasing, so the block's last key ends
+  // at query tile ceil(hi / 64) - 1, a wave's sub-tile is past every key from hi[its last key] on and holds an
+  // upper edge from hi[its first key] on (lanes 31 / 0: wave-uniform)
+  const int hi_k = DOC ? P.bounds[((long)P.B + b) * T + key] : 0;
+  const int hi_w0 = DOC ? __builtin_amdgcn_readfirstlane(hi_k) : 0;
+  const int hi_w1 = DOC ? __builtin_amdgcn_readlane(hi_k, 31) : 0;
+  const int t_end = WIN   ? min(nT, (kblk0 + kBlockRows - 1 + W - 1) / kTile + 1)
+                    : DOC ? max(t_begin + 1, min(nT, (P.bounds[((long)P.B + b) * T + kblk0 + kBlockRows - 1] +
+                                                      kTile - 1) / kTile))
+                          : nT;
   const int nit = (t_end - t_begin + KS - 1) / KS;   // iterations per head
   const int njobs = G * nit;
 
@@ -836,6 +918,7 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
           float p = __builtin_amdgcn_exp2f(sa[i]);
           if (CAUSAL && diag && key > qb + 8 * g4 + 4 * h + e) p = 0.f;
           if (WIN && ledge && qb + 8 * g4 + 4 * h + e >= key + W) p = 0.f;
+          if (DOC && ledge && qb + 8 * g4 + 4 * h + e >= hi_k) p = 0.f;
           if (DROP) {     // dS = fma(p keep, dP', p D): the masked probability carries the keep bit
             const float pdv = __uint_as_float(__float_as_uint(p) & keep_mask_v(Mv[e], jbit));
             pd[i] = pdv;
@@ -860,7 +943,8 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
       }
     };
     if (t < t_end) {
-      if (D == 128 && (!CAUSAL || t * kTile >= k0 + 31) && (!WIN || t * kTile + kTile - 1 < k0 + W)) {
+      if (D == 128 && (!CAUSAL || t * kTile >= k0 + 31) && (!WIN || t * kTile + kTile - 1 < k0 + W) &&
+          (!DOC || t * kTile + kTile - 1 < hi_w0)) {
         // full tile (no mask): both sub-tiles' S/dP first, so the second pair's MFMAs overlap the
         // first sub-tile's softmax, and its dV/dK MFMAs overlap the second softmax
         f32x16 sa0, dp0, sa1, dp1, pd, ds;
@@ -876,9 +960,10 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
           const int qb = t * kTile + 32 * mm;
           if (CAUSAL && qb + 31 < k0) continue;   // every query < every key of this wave
           if (WIN && qb >= k0 + 31 + W) continue;  // every query >= every key + W
+          if (DOC && qb >= hi_w1) continue;        // every query >= hi of every key
           f32x16 sa, dp, pd, ds;
           sdp(mm, sa, dp);
-          softmax(mm, sa, dp, qb < k0 + 31, WIN && qb + 31 >= k0 + W, pd, ds);
+          softmax(mm, sa, dp, qb < k0 + 31, (WIN && qb + 31 >= k0 + W) || (DOC && qb + 31 >= hi_w0), pd, ds);
           accum(mm, pd, ds);
         }
       }
@@ -927,6 +1012,14 @@ __global__ __launch_bounds__(256) void dkdv_reduce_kernel(const float* __restric
 // causal D = 64 with dropout spills at 3 (40 B of scratch per lane): 2 splits there (188 VGPRs, no scratch)
 template <int D, bool C = false>
 constexpr int dq_ks() { return D == 64 ? (C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > 2 ? 2 : DLTB_DQ_KS64) : 2; }
+// document bounds: D = 64 stays at 2 (without dropout 3 needs 20 B of scratch per lane); D = 128 with dropout
+// needs 20 B at 2 splits (256 VGPRs at 2 waves / SIMD) in every formulation of the mask that was tried, and runs
+// unsplit: 256 threads may use the AGPR half of the register file.  That kernel keeps the two splits' partial
+// sums apart (even and odd tiles counted from t_lo, each in its own accumulator, added at the end like the LDS
+// merge), so its dQ equals the two-split causal / windowed kernels' bit for bit
+// (profiles/attention_docmask_resources.txt)
+template <int D, bool DR>
+constexpr int dq_ks_doc() { return D == 128 && DR ? 1 : dq_ks<D, true>(); }
 template <int D>
 constexpr int dq_nst() { return D == 64 ? 3 : 2; }   // LDS ring depth, as the forward's
 template <int D>
@@ -938,9 +1031,10 @@ constexpr int dq_smem_bytes() {
   return ring > merge ? ring : merge;
 }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false>
 __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
   constexpr int TB = kTile * D * 2;
   constexpr int NACC = D / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1001,7 +1095,12 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   const uint32_t* mrow = DROP ? mbase + (long)h * T + qi : nullptr;
   const int nt = CAUSAL ? min(nT, (qb * kBlockRows + kBlockRows - 1) / kTile + 1) : nT;
   const int W = WIN ? P.window : 0;              // the forward's tile range: t_lo .. nt - 1
-  const int t_lo = WIN ? max(0, qb * kBlockRows - W + 1) / kTile : 0;
+  const int lo_q = DOC ? P.bounds[(long)b * T + qi] : 0;     // document bounds, as in the forward
+  const int lo_w0 = DOC ? __builtin_amdgcn_readfirstlane(lo_q) : 0;
+  const int lo_w1 = DOC ? __builtin_amdgcn_readlane(lo_q, 31) : 0;
+  const int t_lo = WIN   ? max(0, qb * kBlockRows - W + 1) / kTile
+                   : DOC ? min(max(P.bounds[(long)b * T + qb * kBlockRows], 0), qb * kBlockRows) / kTile
+                         : 0;
   const int nit = (nt - t_lo + KS - 1) / KS;
   const bf16_t* kbase = P.k + (long)b * T * P.k_stride + hk * D;
   const bf16_t* vbase = P.v + (long)b * T * P.v_stride + hk * D;
@@ -1032,9 +1131,15 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
 #pragma unroll
   for (int i = 0; i < NST - 1; ++i) issue(i);
 
-  f32x16 dq[NACC];
+  // EMU2: one wave sums what the two key splits of the causal kernel sum, in their order (dq_ks_doc)
+  constexpr bool EMU2 = DOC && D == 128 && DROP && KS == 1;
+  f32x16 dq[NACC], dq_odd[EMU2 ? NACC : 1];
 #pragma unroll
   for (int dt = 0; dt < NACC; ++dt) dq[dt] = f32x16{};
+  if constexpr (EMU2) {
+#pragma unroll
+    for (int dt = 0; dt < NACC; ++dt) dq_odd[dt] = f32x16{};
+  }
 
   for (int it = 0; it < nit; ++it) {
     const int t = t_lo + it * KS + sp;
@@ -1058,15 +1163,17 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
       }
     };
     // softmax / dS of sub-tile n and dQ^T += K^T dS^T
-    auto fin = [&](int n, const f32x16& sa, const f32x16& dp) {
+    auto fin = [&](int n, const f32x16& sa, const f32x16& dp, auto ODD) {
       const bool diag = CAUSAL && kv0 + 32 * n + 31 > q0;
       const bool ledge = WIN && kv0 + 32 * n <= q0 + 31 - W;     // some key <= some query - W
+      const bool dedge = DOC && kv0 + 32 * n < lo_w1;            // some key < lo of some query
       f32x16 ds;
       static_for<16>([&](auto I) {
         constexpr int i = I;
         float p = __builtin_amdgcn_exp2f(sa[i]);
         if (diag && kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h > qi) p = 0.f;
         if (ledge && kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h <= qi - W) p = 0.f;
+        if (dedge && kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h < lo_q) p = 0.f;
         const float dpv = DROP ? (n == 0 ? keep_sel<mask_bit(0, i)>(dp[i], nd, mw)
                                          : keep_sel<mask_bit(1, i)>(dp[i], nd, mw)) : dp[i];
         ds[i] = p * dpv;
@@ -1076,7 +1183,8 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
         const bfx8 sf = pack_frag<D>(ds, s2);
 #pragma unroll
         for (int dt = 0; dt < NACC; ++dt)
-          dq[dt] = mfma32(tr_frag<D>(kt, 32 * n + 16 * s2, dt * 32, lane), sf, dq[dt]);
+          if constexpr (EMU2 && ODD) dq_odd[dt] = mfma32(tr_frag<D>(kt, 32 * n + 16 * s2, dt * 32, lane), sf, dq_odd[dt]);
+          else dq[dt] = mfma32(tr_frag<D>(kt, 32 * n + 16 * s2, dt * 32, lane), sf, dq[dt]);
       }
     };
     if (t < nt) {
@@ -1085,12 +1193,20 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
         for (int n = 0; n < 2; ++n) {
           if (CAUSAL && kv0 + 32 * n > q0 + 31) continue;
           if (WIN && kv0 + 32 * n + 31 <= q0 - W) continue;      // every key <= every query - W
+          if (DOC && kv0 + 32 * n + 31 < lo_w0) continue;        // every key < lo of every query
           f32x16 sa, dp;
           sdp(n, sa, dp);
-          fin(n, sa, dp);
+          if (EMU2 && (it & 1)) fin(n, sa, dp, IC<1>{});     // wave-uniform
+          else fin(n, sa, dp, IC<0>{});
         }
       }
     }
+  }
+  if constexpr (EMU2) {
+#pragma unroll
+    for (int dt = 0; dt < NACC; ++dt)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dq[dt][i] += dq_odd[dt][i];
   }
   __syncthreads();              // all LDS reads done before the ring is reused for the merge
   if constexpr (KS > 1) {      // splits 1..KS-1 -> LDS -> split 0
@@ -1150,25 +1266,27 @@ long dltb_attn_mask_words(int B, int Hq, int T) { return (long)B * Hq * (T / kTi
 namespace {
 
 // WIN = true: the sliding-window instantiations (causal only), with the key splits of the causal kernels
-template <int D, bool C, bool DR, bool WIN = false>
+// DOC = true: the document-bounds instantiations (causal only, WIN = false), with the windowed key splits
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false>
 void set_attrs() {
-  (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, C, DR, fwd_ks<D, C>(), WIN>,
+  (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, C, DR, fwd_ks<D, C>(), WIN, DOC>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, fwd_smem_bytes<D, fwd_ks<D, C>()>());
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, C, DR, dq_ks<D, C>(), WIN>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, dq_smem_bytes<D, dq_ks<D, C>()>());
-  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > dq_ks<D, C>() && !(WIN && DR))
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, C, DR, DLTB_DQ_KS64, WIN>,
+  constexpr int DQKS = DOC ? dq_ks_doc<D, DR>() : dq_ks<D, C>();
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, C, DR, DQKS, WIN, DOC>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, dq_smem_bytes<D, DQKS>());
+  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > dq_ks<D, C>() && !(WIN && DR) && !DOC)
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, C, DR, DLTB_DQ_KS64, WIN, DOC>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, dq_smem_bytes<D, DLTB_DQ_KS64>());
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<D, C, DR, dkdv_ks<D>(), WIN>,
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<D, C, DR, dkdv_ks<D>(), WIN, DOC>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, dkdv_smem_bytes<D>());
 }
 
-template <int D, bool C, bool DR, bool WIN = false>
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false>
 void launch_fwd(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = fwd_ks<D, C>();
   constexpr int smem = fwd_smem_bytes<D, KS>();
   dim3 grid((a.T / kBlockRows) * a.B * a.Hq);
-  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS, WIN>), grid, dim3(256 * KS), smem, st, a);
+  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS, WIN, DOC>), grid, dim3(256 * KS), smem, st, a);
 }
 
 #define DLTB_ATTN_DISPATCH(FN, D, C, DR, ...)           \
@@ -1187,6 +1305,13 @@ void launch_fwd(const AttnArgs& a, hipStream_t st) {
   do {                                                  \
     if (D == 64) { if (DR) FN<64, true, true, true>(__VA_ARGS__); else FN<64, true, false, true>(__VA_ARGS__); } \
     else         { if (DR) FN<128, true, true, true>(__VA_ARGS__); else FN<128, true, false, true>(__VA_ARGS__); } \
+  } while (0)
+
+// the document-bounds (causal) instantiations
+#define DLTB_ATTN_DISPATCH_DOC(FN, D, DR, ...)          \
+  do {                                                  \
+    if (D == 64) { if (DR) FN<64, true, true, false, true>(__VA_ARGS__); else FN<64, true, false, false, true>(__VA_ARGS__); } \
+    else         { if (DR) FN<128, true, true, false, true>(__VA_ARGS__); else FN<128, true, false, false, true>(__VA_ARGS__); } \
   } while (0)
 
 // A window of T or more keys is plain causal attention and runs the causal kernels (bitwise the same result);
@@ -1211,6 +1336,16 @@ void dltb_attn_init_attributes() {
   set_attrs<64, true, true, true>();
   set_attrs<128, true, false, true>();
   set_attrs<128, true, true, true>();
+  set_attrs<64, true, false, false, true>();
+  set_attrs<64, true, true, false, true>();
+  set_attrs<128, true, false, false, true>();
+  set_attrs<128, true, true, false, true>();
+}
+
+void dltb_attn_doc_bounds(const int64_t* idx, int* bounds, int B, int T, int64_t eos, int window, hipStream_t st) {
+  // a window of T or more keys masks nothing (and i + window must not overflow)
+  hipLaunchKernelGGL(attn_doc_bounds_kernel, dim3(B), dim3(256), 0, st, idx, bounds, B, T, eos,
+                     window > 0 && window < T ? window : 0);
 }
 
 void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const int64_t* seed,
@@ -1222,13 +1357,18 @@ void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const 
 void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
-                   hipStream_t st, int window) {
+                   hipStream_t st, int window, const int* bounds) {
   AttnArgs a = make_args(q, k, v, qs, ks, vs, B, T, Hq, Hkv, scale, causal, thr16, drop_scale,
                          nullptr, 0);
   a.out = (bf16_t*)o;
   a.out_stride = os;
   a.lse = lse;
   a.mask = mask;
+  if (bounds) {        // causal, window = 0 (checked by the caller): the window is folded into the bounds
+    a.bounds = bounds;
+    DLTB_ATTN_DISPATCH_DOC(launch_fwd, D, thr16 != 0, a, st);
+    return;
+  }
   if (windowed(causal, window, T)) {
     a.window = window;
     DLTB_ATTN_DISPATCH_WIN(launch_fwd, D, thr16 != 0, a, st);
@@ -1256,11 +1396,11 @@ void dltb_attn_bwd_delta(const void* o, const void* dout, float* delta, long os,
 }
 
 namespace {
-template <int D, bool C, bool DR, bool WIN = false>
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false>
 void launch_dkdv(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = dkdv_ks<D>();
 
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, C, DR, KS, WIN>), dim3((a.T / kBlockRows) * a.B * a.Hkv * a.gsplit),
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, C, DR, KS, WIN, DOC>), dim3((a.T / kBlockRows) * a.B * a.Hkv * a.gsplit),
                      dim3(256 * KS), dkdv_smem_bytes<D>(), st, a);
   if (a.gsplit > 1) {
     const long rows = (long)a.B * a.T;
@@ -1269,24 +1409,25 @@ void launch_dkdv(const AttnArgs& a, hipStream_t st) {
                        a.part, a.gsplit, rows, cols, a.out, a.out_stride, a.out2, a.out2_stride);
   }
 }
-template <int D, bool C, bool DR, int KS, bool WIN>
+template <int D, bool C, bool DR, int KS, bool WIN, bool DOC>
 void launch_dq_ks(const AttnArgs& a, hipStream_t st) {
   constexpr int smem = dq_smem_bytes<D, KS>();
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, C, DR, KS, WIN>), dim3((a.T / kBlockRows) * a.B * a.Hq), dim3(256 * KS),
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, C, DR, KS, WIN, DOC>), dim3((a.T / kBlockRows) * a.B * a.Hq), dim3(256 * KS),
                      smem, st, a);
 }
 // Causal D = 64 dQ: 2 key splits short, 3 from T = 1024 (A/B, profiles/attention_causal_d64_ks_r5.txt: T 2048
 // 35.4 -> 32.4 us with 3; B4 T512 12.6 with 2 against 13.1)
 // The windowed kernel with dropout stays at 2 for every T: at 3 it needs 24 B of scratch per lane
 // (profiles/attention_window_resources.txt), and no windowed instantiation may spill.
+// The document-bounds kernels take dq_ks_doc splits for every T.
 constexpr int kDqCausalLongT = 1024;
-template <int D, bool C, bool DR, bool WIN = false>
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false>
 void launch_dq(const AttnArgs& a, hipStream_t st) {
-  constexpr int KS = dq_ks<D, C>();
-  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > KS && !(WIN && DR)) {
-    if (a.T >= kDqCausalLongT) return launch_dq_ks<D, C, DR, DLTB_DQ_KS64, WIN>(a, st);
+  constexpr int KS = DOC ? dq_ks_doc<D, DR>() : dq_ks<D, C>();
+  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > KS && !(WIN && DR) && !DOC) {
+    if (a.T >= kDqCausalLongT) return launch_dq_ks<D, C, DR, DLTB_DQ_KS64, WIN, DOC>(a, st);
   }
-  launch_dq_ks<D, C, DR, KS, WIN>(a, st);
+  launch_dq_ks<D, C, DR, KS, WIN, DOC>(a, st);
 }
 }  // namespace
 
@@ -1306,7 +1447,13 @@ void launch_dq(const AttnArgs& a, hipStream_t st) {
 // T 2048 / W 512 (128 workgroups: 2 -> 66.8 us, 1 -> 100.6, 4 -> 81.7).  At T 8192 / W 4096, where half of
 // the key blocks still sweep a causal triangle, it leaves the grid unsplit (1172 us) although 2 measured
 // 974 us; the dispatch order of the unsplit grid and a work-based rule for W near T are not measured.
-int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal, int window) {
+//
+// With document bounds the work per key block depends on the tokens (a key block sweeps the query tiles up to the
+// end of its last key's document, or of its window), so no fixed rule can balance it.  The split is chosen as
+// for the window -- fill the chip once -- which is exact for documents much shorter than T and leaves a single
+// row-long document (the causal triangle) at half the causal split.  UNMEASURED against forced splits:
+// profiles/attention_docmask.txt times the bounds kernels with this rule only.
+int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal, int window, int bounds) {
   const int G = Hq / Hkv;
   if (!causal || G < 2) return 1;
   static const int forced = [] {
@@ -1315,7 +1462,7 @@ int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal, int window)
   }();
   if (forced > 0) return G % forced == 0 ? forced : 1;
   const long wgs = (long)(T / kBlockRows) * B * Hkv;
-  const long target = windowed(causal, window, T) ? 256 : 2L * 256;
+  const long target = windowed(causal, window, T) || bounds ? 256 : 2L * 256;
   int s = 1;
   while (s < G && wgs * s < target && G % (2 * s) == 0) s *= 2;
   return s;
@@ -1327,7 +1474,7 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
                         void* out2, long qs, long ks, long vs, long dos, long outs, long out2s,
                         int B, int T, int Hq, int Hkv, int D, float scale, int causal,
                         uint32_t thr16, float drop_scale, hipStream_t st, const void* o, long os,
-                        int gsplit, float* part_buf, int window) {
+                        int gsplit, float* part_buf, int window, const int* bounds) {
   AttnArgs a = make_args(q, k, v, qs, ks, vs, B, T, Hq, Hkv, scale, causal, thr16, drop_scale,
                          nullptr, 0);
   if (part == 0 && gsplit > 1 && part_buf && (Hq / Hkv) % gsplit == 0) {
@@ -1345,6 +1492,14 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
   a.out2_stride = out2s;
   a.o = part == 1 ? (const bf16_t*)o : nullptr;     // dQ pass computes and writes delta itself
   a.o_stride = os;
+  if (bounds) {        // causal, window = 0 (checked by the caller): the window is folded into the bounds
+    a.bounds = bounds;
+    if (part == 0)
+      DLTB_ATTN_DISPATCH_DOC(launch_dkdv, D, thr16 != 0, a, st);
+    else
+      DLTB_ATTN_DISPATCH_DOC(launch_dq, D, thr16 != 0, a, st);
+    return;
+  }
   if (windowed(causal, window, T)) {
     a.window = window;
     if (part == 0)

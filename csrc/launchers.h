@@ -103,7 +103,7 @@ void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const 
 void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
-                   hipStream_t st, int window = 0);
+                   hipStream_t st, int window = 0, const int* bounds = nullptr);
 void dltb_attn_bwd_delta(const void* o, const void* dout, float* delta, long os, long dos, int B,
                          int T, int Hq, int D, hipStream_t st);
 void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, const void* dout,
@@ -111,9 +111,15 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
                         void* out2, long qs, long ks, long vs, long dos, long outs, long out2s,
                         int B, int T, int Hq, int Hkv, int D, float scale, int causal,
                         uint32_t thr16, float drop_scale, hipStream_t st, const void* o = nullptr,
-                        long os = 0, int gsplit = 1, float* part_buf = nullptr, int window = 0);
+                        long os = 0, int gsplit = 1, float* part_buf = nullptr, int window = 0,
+                        const int* bounds = nullptr);
 // dK/dV workgroups per KV head for a causal GQA backward (1 = one workgroup sums the whole group)
-int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal, int window = 0);
+int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal, int window = 0, int bounds = 0);
+// document bounds of packed sequences: int32 [2][B][T] (lo plane, hi plane) from idx [B][T], one launch and no
+// host sync.  ``bounds`` arguments above: that buffer (causal only, window = 0: it is folded in here).  The
+// attention kernels trust it (non-decreasing planes, lo[i] <= i < hi[i]); hand-made bounds are not validated.
+void dltb_attn_doc_bounds(const int64_t* idx, int* bounds, int B, int T, int64_t eos, int window,
+                          hipStream_t st);
 void dltb_attn_init_attributes();
 
 // ---- batched column reductions (colreduce.hip)

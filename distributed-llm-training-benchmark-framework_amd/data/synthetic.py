@@ -17,10 +17,57 @@ import torch
 
 
 class SyntheticDataset:
-    def __init__(self, vocab_size: int = 32000, seq_len: int = 2048, size: int = 1000, seed: int = 42):
+    """``doc_len = N`` packs documents into every row: their lengths are drawn uniformly in [1, 2N - 1] (mean N)
+    from the same private generator AFTER the token table (the tokens are those of the unpacked table), a
+    document that crosses a row end is cut there, ``eos_id`` sits at each document's last position and every
+    other occurrence of ``eos_id`` becomes ``(eos_id + 1) % vocab_size``.  With the defaults the table is
+    bit-identical to the unpacked one."""
+
+    def __init__(self, vocab_size: int = 32000, seq_len: int = 2048, size: int = 1000, seed: int = 42,
+                 doc_len: int = None, eos_id: int = None):
         g = torch.Generator().manual_seed(seed)
         self.data = torch.randint(0, vocab_size, (size, seq_len), generator=g, dtype=torch.int64)
         self.size, self.seq_len, self.vocab_size = size, seq_len, vocab_size
+        self.doc_len, self.eos_id = doc_len, eos_id
+        if doc_len is None:
+            if eos_id is not None:
+                raise ValueError("eos_id is only used together with doc_len")
+            return
+        if isinstance(doc_len, bool) or not isinstance(doc_len, int) or doc_len < 1:
+            raise ValueError(f"doc_len must be an integer >= 1 or None, got {doc_len!r}")
+        if eos_id is None:
+            self.eos_id = eos_id = vocab_size - 1
+        if not 0 <= eos_id < vocab_size or vocab_size < 2:
+            raise ValueError(f"eos_id must be in [0, vocab_size) with vocab_size >= 2, got {eos_id!r}")
+        # document lengths in column blocks of about one row's worth (mean doc_len each), drawn until every row is
+        # covered: the table of lengths stays near size * seq_len / doc_len entries.  Ends past the row are dropped
+        # and the row's last position always ends a document (the cut).
+        is_end = torch.zeros(size, seq_len, dtype=torch.bool)
+        rows = torch.arange(size)[:, None]
+        start = torch.zeros(size, 1, dtype=torch.int64)                   # first position not yet in a document
+        block = seq_len // doc_len + 8
+        while int(start.min()) < seq_len:
+            lens = torch.randint(1, 2 * doc_len, (size, block), generator=g, dtype=torch.int64)
+            ends = start + lens.cumsum(1) - 1
+            keep = ends < seq_len
+            is_end[rows.expand_as(ends)[keep], ends[keep]] = True
+            start = ends[:, -1:] + 1
+        is_end[:, -1] = True
+        self.data[self.data == eos_id] = (eos_id + 1) % vocab_size
+        self.data[is_end] = eos_id
+
+    def visible_pairs_per_row(self, window: int = None) -> float:
+        """Mean number of visible (query, key) pairs of a row under the causal document mask, counted from the
+        table: a document of n tokens has n (n + 1) / 2.  ``window`` = W caps every query at W keys."""
+        T = self.seq_len
+        pos = torch.arange(T).expand(self.size, T)
+        eos = self.data == self.eos_id if self.doc_len is not None else torch.zeros_like(self.data, dtype=torch.bool)
+        last = torch.where(eos, pos, torch.full_like(pos, -1)).cummax(1).values
+        lo = torch.cat([torch.zeros_like(pos[:, :1]), last[:, :-1] + 1], 1)
+        seen = pos - lo + 1
+        if window:
+            seen = seen.clamp(max=int(window))
+        return float(seen.sum().item()) / self.size
 
     def __len__(self):
         return self.size

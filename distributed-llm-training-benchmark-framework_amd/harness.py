@@ -60,6 +60,11 @@ def build_parser():
     p.add_argument("--sliding-window", type=int, default=None, metavar="N",
                    help="causal tiers (M7B, M7B_narrow, mtiny): query i attends to keys i - N < j <= i (N keys "
                         "including its own, the Mistral mask); default: no window")
+    p.add_argument("--doc-len", type=int, default=None, metavar="N",
+                   help="causal tiers: pack documents of mean length N (uniform in [1, 2N - 1]) into every row and "
+                        "mask attention at the document boundaries; default: every row is one document")
+    p.add_argument("--eos-id", type=int, default=None, metavar="ID",
+                   help="token that ends a document with --doc-len (default: vocab_size - 1)")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -192,6 +197,12 @@ def train(args):
         if getattr(args, "sliding_window", None) is not None:
             mcfg.sliding_window = args.sliding_window
             mcfg.validate()
+        doc_len = getattr(args, "doc_len", None)
+        eos_id = None
+        if doc_len is not None:
+            eos_id = args.eos_id if getattr(args, "eos_id", None) is not None else mcfg.vocab_size - 1
+            mcfg.doc_eos_id = eos_id
+            mcfg.validate()
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         n_params = model.num_params()
@@ -201,9 +212,10 @@ def train(args):
         if is_main:
             print(f"[Rank {rank}] engine={type(engine).__name__} accum={engine.accum} clip={ecfg.grad_clip} "
                   f"sched={'WarmupLR' if ecfg.scheduler else 'constant'} dtype={engine.compute_dtype}", flush=True)
-        ds = SyntheticDataset(mcfg.vocab_size, args.seq_len, size=1000, seed=42)
+        ds = SyntheticDataset(mcfg.vocab_size, args.seq_len, size=1000, seed=42, doc_len=doc_len, eos_id=eos_id)
         if is_main:
-            print(f"SyntheticDataset: {len(ds)} samples, seq_len={args.seq_len}", flush=True)
+            print(f"SyntheticDataset: {len(ds)} samples, seq_len={args.seq_len}"
+                  + (f", documents of mean length {doc_len} ending in token {eos_id}" if doc_len else ""), flush=True)
         batches = make_batcher(args.data_loader, ds, args.per_device_batch, world, rank, args.strategy, device)
         if device.type == "cuda":
             torch.cuda.reset_peak_memory_stats(device)
@@ -313,7 +325,10 @@ def train(args):
                              args.per_device_batch, args.grad_accum, mean_step, mean_loss, peak)
         ev_times = [a.elapsed_time(b) / 1e3 for a, b in step_events] if step_events else []
         tokens_step = args.per_device_batch * args.seq_len * world
-        flops_tok = mcfg.train_flops_per_token(args.seq_len)
+        # a document mask depends on the data: count the table's visible pairs (window included), as the window
+        # formula counts its band
+        pairs = ds.visible_pairs_per_row(mcfg.sliding_window) if doc_len is not None else None
+        flops_tok = mcfg.train_flops_per_token(args.seq_len, pairs)
         tflops_gpu = (tokens_step / world) * flops_tok / mean_step / 1e12 if mean_step > 0 else 0.0
         extended = {
             "record_file_semantics": "tokens_per_sec = per_device_batch*seq_len*world_size / mean_step_time_sec "
@@ -327,6 +342,10 @@ def train(args):
             "tflops_per_gpu": tflops_gpu, "mfu_vs_2.5PF_dense_bf16": tflops_gpu * 1e12 / MI355X_DENSE_BF16_FLOPS,
             "train_flops_per_token": flops_tok, "params": n_params, "trainable_params": n_params,
             "model": mcfg.to_dict(), "engine": type(engine).__name__,
+            "data": {"doc_len": doc_len, "eos_id": eos_id,
+                     # visible (query, key) pairs of the table over the causal T (T + 1) / 2
+                     "visible_pair_fraction": (pairs / (args.seq_len * (args.seq_len + 1) / 2.0)
+                                               if pairs is not None else None)},
             "hip_graphs": bool(runner is not None and runner.graphs and not runner.disabled),
             "engine_config": {k: (str(v) if isinstance(v, torch.dtype) else v) for k, v in vars(ecfg).items()},
             "optimizer_steps": engine.opt_steps, "last_lr": engine.last_lr,
@@ -371,6 +390,16 @@ def main(argv=None):
             parser.error("--sliding-window must be >= 1")
         if not get_model_config(args.tier, args.seq_len).causal:
             parser.error(f"--sliding-window needs a causal tier; tier {args.tier} attends non-causally")
+    if args.doc_len is not None:
+        cfg0 = get_model_config(args.tier, args.seq_len)
+        if args.doc_len < 1:
+            parser.error("--doc-len must be >= 1")
+        if not cfg0.causal:
+            parser.error(f"--doc-len needs a causal tier; tier {args.tier} attends non-causally")
+        if args.eos_id is not None and not 0 <= args.eos_id < cfg0.vocab_size:
+            parser.error(f"--eos-id must be in [0, {cfg0.vocab_size}) for tier {args.tier}")
+    elif args.eos_id is not None:
+        parser.error("--eos-id is only used together with --doc-len")
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:
         args.deepspeed_config = default_config_path(args.strategy)
         print(f"[dltb] --deepspeed-config not given; using {args.deepspeed_config}", flush=True)

@@ -36,6 +36,9 @@ class ModelConfig:
     tier: str = "custom"
     # causal sliding window W: query i sees keys i - W < j <= i (W keys including its own); None = no window
     sliding_window: Optional[int] = None
+    # packed sequences: a token equal to doc_eos_id ends a document (and belongs to it); attention does not cross
+    # document boundaries.  None = every row is one document.  Causal only; composes with sliding_window.
+    doc_eos_id: Optional[int] = None
 
     def __post_init__(self):
         self.validate()
@@ -48,6 +51,12 @@ class ModelConfig:
                 raise ValueError(f"sliding_window must be an integer >= 1 or None, got {w!r}")
             if not self.causal:
                 raise ValueError("sliding_window needs causal=True")
+        e = self.doc_eos_id
+        if e is not None:
+            if isinstance(e, bool) or not isinstance(e, int) or not 0 <= e < self.vocab_size:
+                raise ValueError(f"doc_eos_id must be an integer in [0, vocab_size) or None, got {e!r}")
+            if not self.causal:
+                raise ValueError("doc_eos_id (document-masked attention) needs causal=True")
 
     @property
     def head_dim(self) -> int:
@@ -77,9 +86,12 @@ class ModelConfig:
         head = 0 if self.tie_embeddings else V * d
         return V * d + L * per_block + d + head
 
-    def train_flops_per_token(self, seq_len: int) -> float:
+    def train_flops_per_token(self, seq_len: int, visible_pairs_per_row: Optional[float] = None) -> float:
         """6 * N_matmul + attention (12 * L * T * d non-causal, halved when causal; with a sliding window
-        W < T a row sees (W (T - W) + W^2 / 2) / T keys on average instead of T / 2)."""
+        W < T a row sees (W (T - W) + W^2 / 2) / T keys on average instead of T / 2).
+        ``visible_pairs_per_row``: the measured number of visible (query, key) pairs of a row of ``seq_len``
+        tokens (a document mask depends on the data: ``SyntheticDataset.visible_pairs_per_row``); it replaces
+        the T^2 / 2 (or window) count.  Without it the result is exactly the formula above."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d
@@ -90,6 +102,8 @@ class ModelConfig:
         w = self.sliding_window
         if self.causal and w is not None and w < seq_len:
             attn = 12 * L * d * (w * (seq_len - w) + w * w / 2.0) / seq_len
+        if visible_pairs_per_row is not None:
+            attn = 12 * L * d * float(visible_pairs_per_row) / seq_len
         return 6.0 * n_mat + attn
 
 

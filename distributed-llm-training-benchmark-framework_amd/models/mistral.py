@@ -100,8 +100,11 @@ class _LayerFn(torch.autograd.Function):
         qkv = F_.linear_fwd(h1, wqkv)
         F_.rope_(qkv, cos, sin, T, Hq + Hkv, D, False)
         qd, kd = Hq * D, Hkv * D
+        # document mask: the forward's bounds (window folded in) replace the window, and stay for the backward
+        bounds = model._cur_bounds
+        window = 0 if bounds is not None else cfg.sliding_window or 0
         o, lse, aux = F_.attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
-                                  1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=cfg.sliding_window or 0)
+                                  1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds)
         a = F_.linear_fwd(o, wo)
         x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
         gu = F_.linear_fwd(h2, wgu)
@@ -111,6 +114,7 @@ class _LayerFn(torch.autograd.Function):
         rt.release_forward(unit)
         ctx.model, ctx.i = model, i
         ctx.saved = (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh)
+        ctx.bounds = bounds
         return x2
 
     @staticmethod
@@ -140,7 +144,9 @@ class _LayerFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                     dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
-                    1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=cfg.sliding_window or 0)
+                    1.0 / math.sqrt(D), True, 0.0, rt.seed, 0,
+                    window=0 if ctx.bounds is not None else cfg.sliding_window or 0, bounds=ctx.bounds)
+        ctx.bounds = None
         F_.rope_(dqkv, cos, sin, T, Hq + Hkv, D, True)      # RoPE is orthogonal: grad = R(-theta) g
         F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
         dh1 = F_.linear_dgrad(dqkv, wqkv, rt.weight_t(unit, 1, wqkv))
@@ -234,6 +240,11 @@ class MistralLM(nn.Module):
         B, T = idx.shape
         assert T <= self.cfg.block_size
         self._cur_bt = (B, T)
+        # packed sequences: the document bounds of this batch, computed once (on the device, from idx, so a
+        # captured step follows its static idx buffer) and shared by every layer's forward and backward
+        self._cur_bounds = None
+        if self.cfg.doc_eos_id is not None:
+            self._cur_bounds = F_.doc_bounds(idx, self.cfg.doc_eos_id, self.cfg.sliding_window or 0)
         anchor = torch.empty((), requires_grad=True)
         x = _EmbedFn.apply(anchor, idx, self)
         for i in range(len(self.unit_blocks)):

@@ -113,9 +113,16 @@ class OracleMistral(nn.Module):
             q, k = _rope(q, cos, sin), _rope(k, cos, sin)
             k = k.repeat_interleave(H // Hkv, 1)
             v = v.repeat_interleave(H // Hkv, 1)
-            if cfg.sliding_window:      # band mask: query i sees keys i - W < j <= i
+            if cfg.sliding_window or cfg.doc_eos_id is not None:
                 i = torch.arange(T, device=idx.device)
-                band = (i[None, :] <= i[:, None]) & (i[None, :] > i[:, None] - cfg.sliding_window)
+                band = (i[None, :] <= i[:, None]).expand(B, 1, T, T)
+                if cfg.sliding_window:      # band mask: query i sees keys i - W < j <= i
+                    band = band & (i[None, :] > i[:, None] - cfg.sliding_window)
+                if cfg.doc_eos_id is not None:
+                    # document mask: token t belongs to document number (EOS tokens before t); an EOS ends its own
+                    eos = (idx == cfg.doc_eos_id).to(torch.int64)
+                    doc = eos.cumsum(1) - eos
+                    band = band & (doc[:, None, :, None] == doc[:, None, None, :])
                 o = F.scaled_dot_product_attention(q, k, v, attn_mask=band)
             else:
                 o = F.scaled_dot_product_attention(q, k, v, is_causal=True)

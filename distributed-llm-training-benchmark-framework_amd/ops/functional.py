@@ -474,32 +474,49 @@ def attn_mask(B, T, Hq, p, seed, site, like):
     return ext().attn_mask(B, T, Hq, p, seed.device_tensor, site, like)
 
 
-def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, mask=None, o_out=None, window=0):
+def doc_bounds(idx, eos_id, window=0):
+    """Document bounds of packed rows ``idx`` [B, T] (int64): int32 ``[2, B, T]``, the ``lo`` and ``hi`` planes of
+    :func:`ref.doc_bounds`, with the sliding window ``window`` folded in.  On the GPU one kernel launch and no
+    host sync, so a captured graph recomputes them from its static ``idx`` buffer on every replay."""
+    if _gpu(idx):
+        return ext().attn_doc_bounds(idx.contiguous(), int(eos_id), int(window or 0))
+    return ref.doc_bounds(idx, int(eos_id), int(window or 0))
+
+
+def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, mask=None, o_out=None, window=0, bounds=None):
     """Returns (o, lse, aux); ``aux`` (the packed dropout mask on the GPU) goes back into attn_bwd.
-    ``window`` = W > 0 (causal only): query i sees keys ``i - W < j <= i``; 0 = no window."""
+    ``window`` = W > 0 (causal only): query i sees keys ``i - W < j <= i``; 0 = no window.
+    ``bounds`` (causal only, with ``window=0``): the document bounds of :func:`doc_bounds`; query i sees keys
+    ``bounds[0, b, i] <= j <= i``.  Hand-made bounds must keep its invariants: the kernels do not check them."""
     ref.check_window(window, causal)
+    ref.check_bounds(bounds, causal, window, B, T)
     if _gpu(q):
         if p > 0 and mask is None:
             mask = ext().attn_mask(B, T, Hq, p, seed.device_tensor, site, q)
         o, lse = ext().attn_fwd(q, k, v, mask if p > 0 else None, B, T, Hq, Hkv, scale, causal, p, o_out,
-                                window)
+                                window, bounds)
         return o, lse, (mask if p > 0 else None)
-    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window)
+    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window, bounds)
     return _into(o_out, o), lse, None
 
 
-def attn_bwd(q, k, v, o, do, lse, aux, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0):
+def attn_bwd(q, k, v, o, do, lse, aux, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0,
+             bounds=None):
     """dQ (query-major kernel, which also forms delta = rowsum(dO * O) for its rows), then dK/dV
-    (key-major kernel, reading that delta).  ``window``: as in :func:`attn_fwd`."""
+    (key-major kernel, reading that delta).  ``window``, ``bounds``: as in :func:`attn_fwd`."""
     ref.check_window(window, causal)
+    ref.check_bounds(bounds, causal, window, B, T)
     if _gpu(q):
         C = ext()
         m = aux if p > 0 else None
         delta = torch.empty_like(lse)
-        C.attn_bwd_part(1, q, k, v, do, lse, delta, m, dq, None, B, T, Hq, Hkv, scale, causal, p, o, window)
-        C.attn_bwd_part(0, q, k, v, do, lse, delta, m, dk, dv, B, T, Hq, Hkv, scale, causal, p, None, window)
+        C.attn_bwd_part(1, q, k, v, do, lse, delta, m, dq, None, B, T, Hq, Hkv, scale, causal, p, o, window,
+                        bounds)
+        C.attn_bwd_part(0, q, k, v, do, lse, delta, m, dk, dv, B, T, Hq, Hkv, scale, causal, p, None, window,
+                        bounds)
     else:
-        ref.attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window)
+        ref.attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window,
+                     bounds)
 
 
 # ------------------------------------------------------------------------------ linear

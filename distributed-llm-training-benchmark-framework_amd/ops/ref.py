@@ -196,8 +196,49 @@ def check_window(window, causal):
         raise ValueError("attention: a sliding window needs causal=True")
 
 
-def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0):
+def check_bounds(bounds, causal, window, B, T):
+    """Document bounds (:func:`doc_bounds`): an int32 ``[2, B, T]`` tensor, only together with the causal mask
+    and instead of ``window`` (the window is folded into the bounds).  ``None`` = no document mask."""
+    if bounds is None:
+        return
+    if not causal:
+        raise ValueError("attention: document bounds need causal=True")
+    if window:
+        raise ValueError("attention: pass either bounds or window (doc_bounds folds the window in)")
+    if bounds.dtype != torch.int32:
+        raise ValueError(f"attention: bounds must be int32, got {bounds.dtype}")
+    if tuple(bounds.shape) != (2, B, T):
+        raise ValueError(f"attention: bounds must have shape [2, {B}, {T}], got {list(bounds.shape)}")
+
+
+def doc_bounds(idx, eos_id, window=0):
+    """Document mask of packed rows as two int32 planes ``[2, B, T]``.  A token equal to ``eos_id`` ends a
+    document and belongs to it.  ``lo[b, i]`` is the first key query i sees (0 without an EOS in ``idx[b, :i]``,
+    else 1 + the last one's position); ``hi[b, j]`` is one past the last query that sees key j (T without an
+    EOS in ``idx[b, j:]``, else 1 + the first one's position).  A sliding window ``W > 0`` is folded in:
+    ``lo[i] = max(lo[i], i - W + 1)``, ``hi[j] = min(hi[j], j + W)``.  Key j is visible to query i iff
+    ``lo[i] <= j <= i`` (the same as ``j <= i < hi[j]``); both planes are non-decreasing along T and
+    ``lo[i] <= i < hi[i]``.  The torch twin of the ``attn_doc_bounds`` kernel, and the CPU path."""
+    if idx.dim() != 2 or idx.dtype != torch.int64:
+        raise ValueError("doc_bounds: idx must be an int64 [B, T] tensor")
+    if window < 0:
+        raise ValueError(f"doc_bounds: window must be >= 0 (0 = no window), got {window}")
+    B, T = idx.shape
+    pos = torch.arange(T, device=idx.device, dtype=torch.int64).expand(B, T)
+    eos = idx == eos_id
+    last = torch.where(eos, pos, torch.full_like(pos, -1)).cummax(1).values       # last EOS at or before i
+    lo = torch.cat([torch.zeros_like(pos[:, :1]), last[:, :-1] + 1], 1)           # ... strictly before i, + 1
+    first = torch.where(eos, pos, torch.full_like(pos, T - 1)).flip(1).cummin(1).values.flip(1)
+    hi = first + 1                                                                 # first EOS at or after j, + 1
+    if window > 0:
+        lo = torch.maximum(lo, pos - window + 1)
+        hi = torch.minimum(hi, pos + window)
+    return torch.stack([lo, hi]).to(torch.int32)
+
+
+def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0, bounds=None):
     check_window(window, causal)
+    check_bounds(bounds, causal, window, B, T)
     qh = _f(q).reshape(B, T, Hq, D).transpose(1, 2)              # [B,Hq,T,D]
     kh = _f(k).reshape(B, T, Hkv, D).transpose(1, 2)
     if Hq != Hkv:
@@ -208,6 +249,9 @@ def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0):
         if 0 < window < T:                                            # keys j <= i - W are out of the band
             m |= torch.ones(T, T, dtype=torch.bool, device=q.device).tril(-window)
         s = s.masked_fill(m, float("-inf"))
+        if bounds is not None:                                        # keys j < lo[b, i] are other documents
+            j = torch.arange(T, device=q.device)
+            s = s.masked_fill((j[None, None, :] < bounds[0].to(q.device)[:, :, None])[:, None], float("-inf"))
     return s
 
 
@@ -220,9 +264,9 @@ def _attn_keep(B, Hq, T, p, seed, site, device):
     return attn_keep_mask(s, rows, cols, p).view(B, Hq, T, T)
 
 
-def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0):
+def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0, bounds=None):
     D = q.shape[1] // Hq
-    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window)
+    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds)
     lse = torch.logsumexp(s, -1)                                      # [B,Hq,T]
     pr = torch.exp(s - lse[..., None])
     keep = _attn_keep(B, Hq, T, p, seed, site, q.device)
@@ -235,10 +279,11 @@ def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0):
     return o.to(q.dtype), _f(lse).contiguous()
 
 
-def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0):
+def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0,
+             bounds=None):
     D = q.shape[1] // Hq
     G = Hq // Hkv
-    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window)
+    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds)
     pr = torch.exp(s - lse.view(B, Hq, T)[..., None])
     keep = _attn_keep(B, Hq, T, p, seed, site, q.device)
     z = torch.ones_like(pr) if keep is None else keep.to(pr.dtype) / (1.0 - p)   # fp64 inputs stay fp64

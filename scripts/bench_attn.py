@@ -3,6 +3,7 @@
 
     python scripts/bench_attn.py [--iters 50]
     python scripts/bench_attn.py --window 4096 --seq-lens 8192,16384,32768   # sliding window vs full causal
+    python scripts/bench_attn.py --doc-len 2048 [--window 4096]              # packed documents vs full causal
 
 Prints one line per kernel: time per call and TFLOP/s (causal FLOPs counted over the visible
 half).  Shapes: TinyGPT-A (B1 T2048 H16 D64, dropout 0.1, non-causal) and Mistral-7B
@@ -137,6 +138,67 @@ def run_window(T, W, iters, rounds, B=1, Hq=32, Hkv=8, D=128, p=0.0):
     return out
 
 
+def doc_tile_counts(bounds, T):
+    """tile_counts for document bounds [2, 1, T] (CPU): the tile ranges of the bounds kernels."""
+    lo, hi = bounds[0, 0].tolist(), bounds[1, 0].tolist()
+    qmaj = kmaj = 0
+    for blk in range(T // 128):
+        qmaj += min(T // 64, (blk * 128 + 127) // 64 + 1) - lo[blk * 128] // 64
+        kmaj += min(T // 64, (hi[blk * 128 + 127] + 63) // 64) - blk * 128 // 64
+    return qmaj, kmaj
+
+
+def run_docs(T, doc_len, W, iters, rounds, B=1, Hq=32, Hkv=8, D=128, p=0.0, seed=0):
+    """Forward, dQ and dK/dV with the document bounds of one seeded layout (documents of mean length
+    ``doc_len``, the harness's SyntheticDataset row 0; window ``W`` folded in) next to full causal attention,
+    alternating as in run_window."""
+    from dltb.data.synthetic import SyntheticDataset
+    C = ext()
+    dev = "cuda"
+    ds = SyntheticDataset(32000, T, size=B, seed=seed, doc_len=doc_len)
+    idx = ds.data.to(dev)
+    bounds = C.attn_doc_bounds(idx, ds.eos_id, W)
+    g = torch.Generator(device=dev).manual_seed(0)
+    qkv = torch.randn(B * T, (Hq + 2 * Hkv) * D, device=dev, dtype=torch.bfloat16, generator=g)
+    q, k, v = qkv[:, :Hq * D], qkv[:, Hq * D:(Hq + Hkv) * D], qkv[:, (Hq + Hkv) * D:]
+    do = torch.randn(B * T, Hq * D, device=dev, dtype=torch.bfloat16, generator=g)
+    scale = D ** -0.5
+    mask = C.attn_mask(B, T, Hq, p, torch.tensor([1234], device=dev, dtype=torch.int64), 1, q) if p > 0 else None
+    dq = torch.empty_like(q)
+    dkv = torch.empty(B * T, 2 * Hkv * D, device=dev, dtype=torch.bfloat16)
+    dk, dv = dkv[:, :Hkv * D], dkv[:, Hkv * D:]
+    fns = {}
+    for name, bd in (("causal", None), ("docs", bounds)):
+        o, lse = C.attn_fwd(q, k, v, mask, B, T, Hq, Hkv, scale, True, p, bounds=bd)
+        delta = C.attn_bwd_delta(o, do, B, T, Hq)
+        fns["fwd", name] = lambda bd=bd: C.attn_fwd(q, k, v, mask, B, T, Hq, Hkv, scale, True, p, bounds=bd)
+        fns["dq", name] = lambda bd=bd, lse=lse, delta=delta: C.attn_bwd_part(
+            1, q, k, v, do, lse, delta, mask, dq, None, B, T, Hq, Hkv, scale, True, p, bounds=bd)
+        fns["dkdv", name] = lambda bd=bd, lse=lse, delta=delta: C.attn_bwd_part(
+            0, q, k, v, do, lse, delta, mask, dk, dv, B, T, Hq, Hkv, scale, True, p, bounds=bd)
+    fns["bounds", "docs"] = lambda: C.attn_doc_bounds(idx, ds.eos_id, W)
+    times = {key: [] for key in fns}
+    for r in range(rounds + 1):                 # round 0 warms up; causal and masked calls alternate
+        for key, fn in fns.items():
+            us = timeit(fn, iters)
+            if r:
+                times[key].append(us)
+    med = {key: sorted(t)[len(t) // 2] for key, t in times.items()}
+    full, doc = tile_counts(T, 0), doc_tile_counts(bounds.cpu(), T)
+    ndocs = int((ds.data[0] == ds.eos_id).sum())
+    print(f"T {T:6d} doc-len {doc_len} window {W} dropout {p}: {ndocs} documents in the row, bounds kernel "
+          f"{med['bounds', 'docs']:.1f} us", flush=True)
+    out = {"documents": ndocs, "bounds_us": med["bounds", "docs"]}
+    for kname, tiles in (("fwd", doc[0] / full[0]), ("dq", doc[0] / full[0]), ("dkdv", doc[1] / full[1])):
+        c, m = med[kname, "causal"], med[kname, "docs"]
+        sc, sm = times[kname, "causal"], times[kname, "docs"]
+        out[kname] = dict(causal_us=c, docs_us=m, time_ratio=m / c, tile_ratio=tiles)
+        print(f"T {T:6d} N {doc_len:5d} W {W:5d} {kname:5s} causal {c:9.1f} us ({min(sc):.1f} .. {max(sc):.1f})  "
+              f"docs {m:9.1f} us ({min(sm):.1f} .. {max(sm):.1f})  time ratio {m / c:.3f}  tile ratio {tiles:.3f}"
+              + ("" if tiles > 0.5 or m < c else "  NOT FASTER"), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
@@ -145,8 +207,15 @@ def main():
     ap.add_argument("--window", type=int, default=0, help="compare this sliding window with full causal attention")
     ap.add_argument("--seq-lens", default="8192,16384,32768", help="sequence lengths of the --window comparison")
     ap.add_argument("--rounds", type=int, default=5, help="interleaved rounds of the --window comparison")
+    ap.add_argument("--doc-len", type=int, default=0,
+                    help="compare document-masked attention (packed documents of this mean length, one seeded "
+                         "layout; composes with --window) with full causal attention at --seq-lens")
+    ap.add_argument("--dropout", type=float, default=0.0, help="attention dropout of the --doc-len comparison")
     a = ap.parse_args()
-    if a.window > 0:
+    if a.doc_len > 0:
+        out = {f"T{T}_N{a.doc_len}_W{a.window}": run_docs(T, a.doc_len, a.window, a.iters, a.rounds, p=a.dropout)
+               for T in (int(x) for x in a.seq_lens.split(","))}
+    elif a.window > 0:
         out = {f"T{T}_W{a.window}": run_window(T, a.window, a.iters, a.rounds)
                for T in (int(x) for x in a.seq_lens.split(","))}
     else:
