@@ -91,6 +91,8 @@ struct AttnArgs {
   float* part;      // bwd_dkdv with gsplit > 1: fp32 partials [gsplit][2][B*T][Hkv*D] (scaled)
   const int* bounds;   // DOC kernels: int32 [2][B][T], plane 0 = lo (first key query i sees), plane 1 = hi (one
                        // past the last query that sees key j); both non-decreasing along T, lo[i] <= i < hi[i]
+  int q_begin, q_rows; // QR kernels: q / o / dout / dq / lse / delta hold only the q_rows queries at positions q_begin ..
+                       // q_begin + q_rows - 1 of each batch row (multiples of kBlockRows); k / v / dk / dv hold all T rows
 };
 
 // accumulator registers 8s .. 8s+7 -> bf16 B operand of k-step s
@@ -351,9 +353,10 @@ constexpr int fwd_stage_bytes() { return 2 * kTile * D * 2 + 1024; }   // K, V, 
 template <int D, int KS = fwd_ks<D>()>
 constexpr int fwd_smem_bytes() { return fwd_nst<D, KS>() * KS * fwd_stage_bytes<D>(); }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false>
 __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !DROP) || !QR, "a query range is causal and without dropout (the packed mask is square)");
   static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
   constexpr bool BAND = WIN || DOC;     // rows / key splits may see no key of a visited tile
   constexpr int TB = kTile * D * 2;
@@ -362,8 +365,12 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
   const int qw = w & 3, sp = w >> 2, stid = tid & 255;
   const int T = P.T, nT = T / kTile;
+  // QR: the grid covers the range's query blocks only; qb, q0, qi stay global positions (every mask and tile
+  // bound below is unchanged) and only the rows of the query-side tensors are taken relative to q_begin
+  const int Tq = QR ? P.q_rows : T, qoff = QR ? P.q_begin : 0;
   int qb, bh;
-  block_coords(T / kBlockRows, P.B * P.Hq, CAUSAL, qb, bh);
+  block_coords(Tq / kBlockRows, P.B * P.Hq, CAUSAL, qb, bh);
+  if (QR) qb += qoff / kBlockRows;
   const int b = bh / P.Hq, hq = bh % P.Hq, hk = hq / (P.Hq / P.Hkv);
   const int q0 = qb * kBlockRows + qw * 32;
   const int qi = q0 + r;
@@ -371,7 +378,7 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
 
   bfx8 qf[D / 16];
   {
-    const bf16_t* qrow = P.q + ((long)b * T + qi) * P.q_stride + hq * D;
+    const bf16_t* qrow = P.q + ((long)b * Tq + qi - qoff) * P.q_stride + hq * D;
 #pragma unroll
     for (int s = 0; s < D / 16; ++s)       // Q c: S' = (Q c) K^T is already in log2 units
       qf[s] = scale_frag(__builtin_bit_cast(bfx8, ld16<uint4>(qrow + 16 * s + 8 * h)), P.scale * kLog2e);
@@ -617,9 +624,9 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   }
   l += __shfl_xor(l, 32, 64);
   const float inv = (DROP ? P.drop_scale : 1.f) / l;
-  bf16_t* orow = P.out + ((long)b * T + qi) * P.out_stride + hq * D;
+  bf16_t* orow = P.out + ((long)b * Tq + qi - qoff) * P.out_stride + hq * D;
   store_acc_rows<D>(orow, oacc, inv, h);
-  if (h == 0) P.lse[((long)b * P.Hq + hq) * T + qi] = (m + __log2f(l)) * 0.69314718055994531f;
+  if (h == 0) P.lse[((long)b * P.Hq + hq) * Tq + qi - qoff] = (m + __log2f(l)) * 0.69314718055994531f;
 }
 
 
@@ -731,9 +738,10 @@ DLTB_DEV void dkdv_finish(const AttnArgs& P, char* smem, f32x16 (&dk)[D / 32], f
   store_acc_rows<D>(dvrow, dv, s_drop, h);
 }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false>
 __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !DROP) || !QR, "a query range is causal and without dropout (the packed mask is square)");
   static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
   constexpr int TB = kTile * D * 2;
   constexpr int SB = dkdv_stage_bytes<D>();   // Q tile, dO tile, lse2[64], delta'[64], mask[64][4]
@@ -789,7 +797,10 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
 #pragma unroll
   for (int dt = 0; dt < NACC; ++dt) { dk[dt] = f32x16{}; dv[dt] = f32x16{}; }
 
-  const int t_begin = CAUSAL ? kblk0 / kTile : 0;
+  const int t_causal = CAUSAL ? kblk0 / kTile : 0;
+  // QR: only the query tiles of [q_begin, q_begin + q_rows) exist; tile numbers and every mask bound stay global
+  const int Tq = QR ? P.q_rows : T, qbeg = QR ? P.q_begin : 0;
+  const int t_begin = QR ? max(t_causal, qbeg / kTile) : t_causal;
   // sliding window W: key j is seen by queries j <= q < j + W, so the block's last key ends at query tile
   // t_end - 1
   const int W = WIN ? P.window : 0;
@@ -799,10 +810,15 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
   const int hi_k = DOC ? P.bounds[((long)P.B + b) * T + key] : 0;
   const int hi_w0 = DOC ? __builtin_amdgcn_readfirstlane(hi_k) : 0;
   const int hi_w1 = DOC ? __builtin_amdgcn_readlane(hi_k, 31) : 0;
-  const int t_end = WIN   ? min(nT, (kblk0 + kBlockRows - 1 + W - 1) / kTile + 1)
-                    : DOC ? max(t_begin + 1, min(nT, (P.bounds[((long)P.B + b) * T + kblk0 + kBlockRows - 1] +
-                                                      kTile - 1) / kTile))
+  const int t_all = WIN   ? min(nT, (kblk0 + kBlockRows - 1 + W - 1) / kTile + 1)
+                    : DOC ? max(t_causal + 1, min(nT, (P.bounds[((long)P.B + b) * T + kblk0 + kBlockRows - 1] +
+                                                       kTile - 1) / kTile))
                           : nT;
+  const int t_end = QR ? min(t_all, (qbeg + Tq) / kTile) : t_all;
+  if (QR && t_begin >= t_end) {       // no query of the range sees this key block (workgroup-uniform): zeros
+    dkdv_finish<D, KS, DROP>(P, smem, dk, dv, kw, sp, lane, h, b, hk, key, gs);
+    return;
+  }
   const int nit = (t_end - t_begin + KS - 1) / KS;   // iterations per head
   const int njobs = G * nit;
 
@@ -828,11 +844,11 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
     // Q / dO tiles straight into the stage buffer by LDS-DMA (it is not being read: the previous
     // reader of this buffer finished before the last barrier)
     char* base = smem + ((j & 1) * KS + sp) * SB;
-    const long r0 = (long)b * T + t * kTile;
+    const long r0 = (long)b * Tq + t * kTile - qbeg;
     GldsTile<D, kTile>::load_sv(P.q + r0 * P.q_stride + hq * D, qoff, base, wv);
     GldsTile<D, kTile>::load_sv(P.dout + r0 * P.do_stride + hq * D, doff, base + TB, wv);
     if (stid < kTile) {   // row constants, loaded straight into the S / dP accumulators
-      const long rc = bq * T + t * kTile;
+      const long rc = bq * Tq + t * kTile - qbeg;
       vl = -P.lse[rc + stid] * kLog2e;
       vd = -P.delta[rc + stid] * inv_s;
     }
@@ -1031,9 +1047,10 @@ constexpr int dq_smem_bytes() {
   return ring > merge ? ring : merge;
 }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false>
 __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !DROP) || !QR, "a query range is causal and without dropout (the packed mask is square)");
   static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
   constexpr int TB = kTile * D * 2;
   constexpr int NACC = D / 32;
@@ -1041,8 +1058,12 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
   const int qw = w & 3, sp = w >> 2, stid = tid & 255;
   const int T = P.T, nT = T / kTile;
+  // QR: the grid covers the range's query blocks only; qb, q0, qi stay global positions (every mask and tile
+  // bound below is unchanged) and only the rows of the query-side tensors are taken relative to q_begin
+  const int Tq = QR ? P.q_rows : T, qoff = QR ? P.q_begin : 0;
   int qb, bh;
-  block_coords(T / kBlockRows, P.B * P.Hq, CAUSAL, qb, bh);
+  block_coords(Tq / kBlockRows, P.B * P.Hq, CAUSAL, qb, bh);
+  if (QR) qb += qoff / kBlockRows;
   const int b = bh / P.Hq, hq = bh % P.Hq, hk = hq / (P.Hq / P.Hkv);
   const int q0 = qb * kBlockRows + qw * 32;
   const int qi = q0 + r;
@@ -1050,8 +1071,8 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
 
   bfx8 qf[D / 16], of[D / 16];
   {
-    const bf16_t* qrow = P.q + ((long)b * T + qi) * P.q_stride + hq * D;
-    const bf16_t* dorow = P.dout + ((long)b * T + qi) * P.do_stride + hq * D;
+    const bf16_t* qrow = P.q + ((long)b * Tq + qi - qoff) * P.q_stride + hq * D;
+    const bf16_t* dorow = P.dout + ((long)b * Tq + qi - qoff) * P.do_stride + hq * D;
 #pragma unroll
     for (int s = 0; s < D / 16; ++s) {
       qf[s] = __builtin_bit_cast(bfx8, ld16<uint4>(qrow + 16 * s + 8 * h));
@@ -1062,7 +1083,7 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   if (P.o) {   // fused delta = rowsum(dO * O) for this row (replaces attn_bwd_delta_kernel)
     // summed in attn_bwd_delta_kernel's order (8-element chunks, then its xor butterfly over the
     // chunks; this lane holds chunks 2s + h), so both paths give bitwise the same delta
-    const bf16_t* orow = P.o + ((long)b * T + qi) * P.o_stride + hq * D;
+    const bf16_t* orow = P.o + ((long)b * Tq + qi - qoff) * P.o_stride + hq * D;
     constexpr int NS = D / 16;
     float cs[NS];
 #pragma unroll
@@ -1080,13 +1101,13 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
 #pragma unroll
       for (int s = 0; s < off; ++s) cs[s] += cs[s + off];
     dlt = cs[0] + __shfl_xor(cs[0], 32, 64);
-    if (sp == 0 && h == 0) const_cast<float*>(P.delta)[bq * T + qi] = dlt;   // read by dK/dV next
+    if (sp == 0 && h == 0) const_cast<float*>(P.delta)[bq * Tq + qi - qoff] = dlt;   // read by dK/dV next
   } else {
-    dlt = P.delta[bq * T + qi];
+    dlt = P.delta[bq * Tq + qi - qoff];
   }
   // row constants as the initial accumulators: S' = (Q c) K^T - lse log2(e) is the exp2 argument
   // and dP' = dO V^T - delta/s, so p = exp2(S'), dS = p (keep ? dP' : -delta/s)
-  const f32x16 nlv = splat16(-P.lse[bq * T + qi] * kLog2e);
+  const f32x16 nlv = splat16(-P.lse[bq * Tq + qi - qoff] * kLog2e);
   const float nd = -dlt * (DROP ? 1.f / P.drop_scale : 1.f);
   const f32x16 ndv = splat16(nd);
 #pragma unroll
@@ -1229,7 +1250,7 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) dq[dt][i] += red0[o * 4 * NF * 64 + (16 * dt + i) * 64];
   }
-  bf16_t* dqrow = P.out + ((long)b * T + qi) * P.out_stride + hq * D;
+  bf16_t* dqrow = P.out + ((long)b * Tq + qi - qoff) * P.out_stride + hq * D;
   store_acc_rows<D>(dqrow, dq, P.scale * (DROP ? P.drop_scale : 1.f), h);
 }
 
@@ -1281,12 +1302,28 @@ void set_attrs() {
                             hipFuncAttributeMaxDynamicSharedMemorySize, dkdv_smem_bytes<D>());
 }
 
-template <int D, bool C, bool DR, bool WIN = false, bool DOC = false>
+// QR = true: the query-range instantiations (causal, no dropout; plain, WIN and DOC), with the key splits and the
+// per-block key walk of the kernels they are a range of
+template <int D, bool WIN, bool DOC>
+void set_attrs_qr() {
+  (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, true, false, fwd_ks<D, true>(), WIN, DOC, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, fwd_smem_bytes<D, fwd_ks<D, true>()>());
+  constexpr int DQKS = DOC ? dq_ks_doc<D, false>() : dq_ks<D, true>();
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, true, false, DQKS, WIN, DOC, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, dq_smem_bytes<D, DQKS>());
+  if constexpr (D == 64 && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > dq_ks<D, true>() && !DOC)
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, true, false, DLTB_DQ_KS64, WIN, DOC, true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, dq_smem_bytes<D, DLTB_DQ_KS64>());
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<D, true, false, dkdv_ks<D>(), WIN, DOC, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, dkdv_smem_bytes<D>());
+}
+
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false>
 void launch_fwd(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = fwd_ks<D, C>();
   constexpr int smem = fwd_smem_bytes<D, KS>();
-  dim3 grid((a.T / kBlockRows) * a.B * a.Hq);
-  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS, WIN, DOC>), grid, dim3(256 * KS), smem, st, a);
+  dim3 grid(((QR ? a.q_rows : a.T) / kBlockRows) * a.B * a.Hq);
+  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS, WIN, DOC, QR>), grid, dim3(256 * KS), smem, st, a);
 }
 
 #define DLTB_ATTN_DISPATCH(FN, D, C, DR, ...)           \
@@ -1314,9 +1351,27 @@ void launch_fwd(const AttnArgs& a, hipStream_t st) {
     else         { if (DR) FN<128, true, true, false, true>(__VA_ARGS__); else FN<128, true, false, false, true>(__VA_ARGS__); } \
   } while (0)
 
+// the query-range (causal, no dropout) instantiations: plain, windowed or with document bounds
+#define DLTB_ATTN_DISPATCH_QR(FN, D, WIN, DOC, ...)     \
+  do {                                                  \
+    if (D == 64) {                                      \
+      if (DOC) FN<64, true, false, false, true, true>(__VA_ARGS__);         \
+      else if (WIN) FN<64, true, false, true, false, true>(__VA_ARGS__);    \
+      else FN<64, true, false, false, false, true>(__VA_ARGS__);            \
+    } else {                                            \
+      if (DOC) FN<128, true, false, false, true, true>(__VA_ARGS__);        \
+      else if (WIN) FN<128, true, false, true, false, true>(__VA_ARGS__);   \
+      else FN<128, true, false, false, false, true>(__VA_ARGS__);           \
+    }                                                   \
+  } while (0)
+
 // A window of T or more keys is plain causal attention and runs the causal kernels (bitwise the same result);
 // only 0 < window < T takes the WIN instantiations.
 bool windowed(int causal, int window, int T) { return causal && window > 0 && window < T; }
+
+// A query range [q_begin, q_end) of the length-T problem; absent (q_end <= 0) or the whole row: the square kernels.
+// The bindings check alignment, causal and p = 0 before a range gets here.
+bool ranged(int q_begin, int q_end, int T) { return q_end > 0 && !(q_begin == 0 && q_end == T); }
 
 }  // namespace
 
@@ -1340,6 +1395,12 @@ void dltb_attn_init_attributes() {
   set_attrs<64, true, true, false, true>();
   set_attrs<128, true, false, false, true>();
   set_attrs<128, true, true, false, true>();
+  set_attrs_qr<64, false, false>();
+  set_attrs_qr<64, true, false>();
+  set_attrs_qr<64, false, true>();
+  set_attrs_qr<128, false, false>();
+  set_attrs_qr<128, true, false>();
+  set_attrs_qr<128, false, true>();
 }
 
 void dltb_attn_doc_bounds(const int64_t* idx, int* bounds, int B, int T, int64_t eos, int window, hipStream_t st) {
@@ -1357,13 +1418,21 @@ void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const 
 void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
-                   hipStream_t st, int window, const int* bounds) {
+                   hipStream_t st, int window, const int* bounds, int q_begin, int q_end) {
   AttnArgs a = make_args(q, k, v, qs, ks, vs, B, T, Hq, Hkv, scale, causal, thr16, drop_scale,
                          nullptr, 0);
   a.out = (bf16_t*)o;
   a.out_stride = os;
   a.lse = lse;
   a.mask = mask;
+  if (ranged(q_begin, q_end, T)) {
+    a.q_begin = q_begin;
+    a.q_rows = q_end - q_begin;
+    a.bounds = bounds;
+    a.window = windowed(causal, window, T) ? window : 0;
+    DLTB_ATTN_DISPATCH_QR(launch_fwd, D, a.window != 0, bounds != nullptr, a, st);
+    return;
+  }
   if (bounds) {        // causal, window = 0 (checked by the caller): the window is folded into the bounds
     a.bounds = bounds;
     DLTB_ATTN_DISPATCH_DOC(launch_fwd, D, thr16 != 0, a, st);
@@ -1396,11 +1465,11 @@ void dltb_attn_bwd_delta(const void* o, const void* dout, float* delta, long os,
 }
 
 namespace {
-template <int D, bool C, bool DR, bool WIN = false, bool DOC = false>
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false>
 void launch_dkdv(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = dkdv_ks<D>();
-
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, C, DR, KS, WIN, DOC>), dim3((a.T / kBlockRows) * a.B * a.Hkv * a.gsplit),
+  // QR: still one workgroup per key block of the whole row; those no query of the range sees store zeros
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, C, DR, KS, WIN, DOC, QR>), dim3((a.T / kBlockRows) * a.B * a.Hkv * a.gsplit),
                      dim3(256 * KS), dkdv_smem_bytes<D>(), st, a);
   if (a.gsplit > 1) {
     const long rows = (long)a.B * a.T;
@@ -1409,11 +1478,11 @@ void launch_dkdv(const AttnArgs& a, hipStream_t st) {
                        a.part, a.gsplit, rows, cols, a.out, a.out_stride, a.out2, a.out2_stride);
   }
 }
-template <int D, bool C, bool DR, int KS, bool WIN, bool DOC>
+template <int D, bool C, bool DR, int KS, bool WIN, bool DOC, bool QR>
 void launch_dq_ks(const AttnArgs& a, hipStream_t st) {
   constexpr int smem = dq_smem_bytes<D, KS>();
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, C, DR, KS, WIN, DOC>), dim3((a.T / kBlockRows) * a.B * a.Hq), dim3(256 * KS),
-                     smem, st, a);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, C, DR, KS, WIN, DOC, QR>),
+                     dim3(((QR ? a.q_rows : a.T) / kBlockRows) * a.B * a.Hq), dim3(256 * KS), smem, st, a);
 }
 // Causal D = 64 dQ: 2 key splits short, 3 from T = 1024 (A/B, profiles/attention_causal_d64_ks_r5.txt: T 2048
 // 35.4 -> 32.4 us with 3; B4 T512 12.6 with 2 against 13.1)
@@ -1421,13 +1490,15 @@ void launch_dq_ks(const AttnArgs& a, hipStream_t st) {
 // (profiles/attention_window_resources.txt), and no windowed instantiation may spill.
 // The document-bounds kernels take dq_ks_doc splits for every T.
 constexpr int kDqCausalLongT = 1024;
-template <int D, bool C, bool DR, bool WIN = false, bool DOC = false>
+// A query range takes the splits of the whole row's kernel (by T, not by the range's length), so its rows come
+// out bit for bit as the whole row's.
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false>
 void launch_dq(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = DOC ? dq_ks_doc<D, DR>() : dq_ks<D, C>();
   if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > KS && !(WIN && DR) && !DOC) {
-    if (a.T >= kDqCausalLongT) return launch_dq_ks<D, C, DR, DLTB_DQ_KS64, WIN, DOC>(a, st);
+    if (a.T >= kDqCausalLongT) return launch_dq_ks<D, C, DR, DLTB_DQ_KS64, WIN, DOC, QR>(a, st);
   }
-  launch_dq_ks<D, C, DR, KS, WIN, DOC>(a, st);
+  launch_dq_ks<D, C, DR, KS, WIN, DOC, QR>(a, st);
 }
 }  // namespace
 
@@ -1474,7 +1545,7 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
                         void* out2, long qs, long ks, long vs, long dos, long outs, long out2s,
                         int B, int T, int Hq, int Hkv, int D, float scale, int causal,
                         uint32_t thr16, float drop_scale, hipStream_t st, const void* o, long os,
-                        int gsplit, float* part_buf, int window, const int* bounds) {
+                        int gsplit, float* part_buf, int window, const int* bounds, int q_begin, int q_end) {
   AttnArgs a = make_args(q, k, v, qs, ks, vs, B, T, Hq, Hkv, scale, causal, thr16, drop_scale,
                          nullptr, 0);
   if (part == 0 && gsplit > 1 && part_buf && (Hq / Hkv) % gsplit == 0) {
@@ -1492,6 +1563,17 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
   a.out2_stride = out2s;
   a.o = part == 1 ? (const bf16_t*)o : nullptr;     // dQ pass computes and writes delta itself
   a.o_stride = os;
+  if (ranged(q_begin, q_end, T)) {
+    a.q_begin = q_begin;
+    a.q_rows = q_end - q_begin;
+    a.bounds = bounds;
+    a.window = windowed(causal, window, T) ? window : 0;
+    if (part == 0)
+      DLTB_ATTN_DISPATCH_QR(launch_dkdv, D, a.window != 0, bounds != nullptr, a, st);
+    else
+      DLTB_ATTN_DISPATCH_QR(launch_dq, D, a.window != 0, bounds != nullptr, a, st);
+    return;
+  }
   if (bounds) {        // causal, window = 0 (checked by the caller): the window is folded into the bounds
     a.bounds = bounds;
     if (part == 0)

@@ -100,10 +100,15 @@ bool dltb_attn_supported(int D, int T);
 long dltb_attn_mask_words(int B, int Hq, int T);
 void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const int64_t* seed,
                     int64_t site, hipStream_t st);
+// q_begin / q_end (trailing, default absent): a query range [q_begin, q_end) of the length-T problem, multiples of
+// 128, causal and thr16 == 0 only.  q / o / dout / dq / lse / delta then hold only those rows of each batch row
+// (positions stay global in every mask), k / v / dk / dv all T; dk / dv rows no query of the range sees are
+// written as zeros.  q_end <= 0 or (0, T): the square kernels, unchanged.
 void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
-                   hipStream_t st, int window = 0, const int* bounds = nullptr);
+                   hipStream_t st, int window = 0, const int* bounds = nullptr, int q_begin = 0,
+                   int q_end = 0);
 void dltb_attn_bwd_delta(const void* o, const void* dout, float* delta, long os, long dos, int B,
                          int T, int Hq, int D, hipStream_t st);
 void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, const void* dout,
@@ -112,7 +117,7 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
                         int B, int T, int Hq, int Hkv, int D, float scale, int causal,
                         uint32_t thr16, float drop_scale, hipStream_t st, const void* o = nullptr,
                         long os = 0, int gsplit = 1, float* part_buf = nullptr, int window = 0,
-                        const int* bounds = nullptr);
+                        const int* bounds = nullptr, int q_begin = 0, int q_end = 0);
 // dK/dV workgroups per KV head for a causal GQA backward (1 = one workgroup sums the whole group)
 int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal, int window = 0, int bounds = 0);
 // document bounds of packed sequences: int32 [2][B][T] (lo plane, hi plane) from idx [B][T], one launch and no

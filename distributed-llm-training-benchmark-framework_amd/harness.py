@@ -13,7 +13,8 @@ Differences that make the numbers honest (recorded in the extended sidecar):
   synchronised wall time of the post-warmup steps divided by their count, max over ranks;
 * per-step losses stay on the device and are read once at the end (the reference syncs every step).
 Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device, --bucket-mb, --dropout, --seed,
---profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier.
+--profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
+--doc-len, --context-parallel, --cp-layout.
 """
 import argparse
 import json
@@ -33,6 +34,7 @@ from .ops import functional as _functional
 from .ops.functional import torch_fallbacks
 from .comm import describe as comm_describe
 from .parallel import STRATEGIES, engine_config, make_engine
+from .parallel import context as _context
 from .parallel.ds_config import ds_precision
 from .parallel.strategy import default_config_path, load_deepspeed_config, load_fsdp_config
 from .results import make_record, print_markers, print_result, write_result
@@ -65,6 +67,12 @@ def build_parser():
                         "mask attention at the document boundaries; default: every row is one document")
     p.add_argument("--eos-id", type=int, default=None, metavar="ID",
                    help="token that ends a document with --doc-len (default: vocab_size - 1)")
+    p.add_argument("--context-parallel", type=int, default=1, metavar="N",
+                   help="causal tiers: split every sequence over groups of N consecutive ranks (all-gather of K | V, "
+                        "query-range attention kernels; parallel/context.py); N must divide the world size")
+    p.add_argument("--cp-layout", choices=["auto", "contiguous", "zigzag"], default="auto",
+                   help="which tokens a rank of a context-parallel group owns; auto: zigzag (balanced causal work) "
+                        "without --sliding-window, contiguous with it")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -148,9 +156,29 @@ def _engine_for(args, model, device):
     return make_engine(model, cfg, device), cfg
 
 
+def tokens_per_micro_step(per_device_batch, seq_len, world, cp=1):
+    """Tokens one micro-step processes over all ranks: the ranks of a context-parallel group share their rows,
+    each holding seq_len / cp tokens of them."""
+    return per_device_batch * (seq_len // cp) * world
+
+
+def check_context_parallel(cp, layout, world, mcfg, seq_len):
+    """The layout ``--context-parallel`` runs with; ValueError when the job cannot run context-parallel."""
+    _context.check_world(cp, world)
+    layout = _context.resolve_layout(layout, mcfg.sliding_window)
+    if cp > 1:
+        if not mcfg.causal:
+            raise ValueError("--context-parallel needs a causal tier (M7B, M7B_narrow, mtiny); the TinyGPT tiers "
+                             "attend non-causally, with dropout and learned positions")
+        _context.check_divisible(layout, seq_len, cp)
+    return layout
+
+
 def train(args):
     world, rank, local_rank = resolve_ranks(args.world_size, args.rank, args.local_rank)
     args.world_size, args.rank, args.local_rank = world, rank, local_rank
+    cp_n = int(getattr(args, "context_parallel", 1) or 1)
+    _context.check_world(cp_n, world)
     auto_bucket = args.bucket_mb is None
     label = args.strategy_label or args.strategy
     if not args.strategy_label and args.strategy == "ddp" and getattr(args, "ddp_shard_optimizer", False):
@@ -203,8 +231,16 @@ def train(args):
             eos_id = args.eos_id if getattr(args, "eos_id", None) is not None else mcfg.vocab_size - 1
             mcfg.doc_eos_id = eos_id
             mcfg.validate()
+        cp_layout = check_context_parallel(cp_n, getattr(args, "cp_layout", "auto"), world, mcfg, args.seq_len)
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
+        cp = None
+        if cp_n > 1:
+            cp = _context.ContextParallel(cp_n, cp_layout, mcfg.sliding_window, world, rank)
+            cp.attach(model)
+            if is_main:
+                print(f"Context parallel: groups of {cp_n} ranks, {cp.layout} layout, rank 0 ranges "
+                      f"{cp.ranges(args.seq_len)}", flush=True)
         n_params = model.num_params()
         if is_main:
             print(f"Model initialized: {n_params / 1e6:.2f}M parameters", flush=True)
@@ -216,7 +252,9 @@ def train(args):
         if is_main:
             print(f"SyntheticDataset: {len(ds)} samples, seq_len={args.seq_len}"
                   + (f", documents of mean length {doc_len} ending in token {eos_id}" if doc_len else ""), flush=True)
-        batches = make_batcher(args.data_loader, ds, args.per_device_batch, world, rank, args.strategy, device)
+        # the ranks of a context-parallel group draw the same rows: the batcher sees the groups
+        batches = make_batcher(args.data_loader, ds, args.per_device_batch, world // cp_n, rank // cp_n,
+                               args.strategy, device)
         if device.type == "cuda":
             torch.cuda.reset_peak_memory_stats(device)
         if is_main:
@@ -231,8 +269,9 @@ def train(args):
         # first window start after an eager window, inside the timed steps -> eager; as fast)
         short_warmup = (args.graphs == "auto" and args.warmup_steps <= engine.accum
                         and os.environ.get("DLTB_GRAPHS") is None)
+        # (context parallel: eager -- the group's gather / reduce-scatter are waited for on the host)
         runner = GraphedStep(engine) if (graphs_enabled(args.graphs, device, world) and not args.profile
-                                         and not args.phase_timers and not short_warmup) else None
+                                         and not args.phase_timers and not short_warmup and cp is None) else None
         timers = PhaseTimers(device) if args.phase_timers else None
         timed_n = max(0, args.steps - args.warmup_steps)
         # per-step losses are COPIED into a device buffer: a graph replay returns the same static
@@ -250,6 +289,8 @@ def train(args):
                 barrier()
                 sync()
                 engine.comm.reset_stats()     # wire accounting over the timed steps only
+                if cp is not None:
+                    cp.comm.reset_stats()
                 t_start = time.perf_counter()
                 if args.profile and is_main:
                     from torch.profiler import ProfilerActivity, profile
@@ -318,13 +359,24 @@ def train(args):
                 print("WARNING: --save-dir skipped: the run did not end on an accumulation boundary", flush=True)
         if args.export_model:
             export_consolidated(engine, args.export_model)
+        cp_ops = {k: dict(v) for k, v in cp.comm.stats.items()} if cp is not None else None
+        if cp is not None and n_loss:
+            # a rank's loss is the mean over its slice of the rows: the group's mean is the rows' loss (one
+            # collective, after the timed region)
+            cp.comm.all_reduce(loss_hist, op="sum", async_op=False)
+            loss_hist /= cp_n
         mean_step = wall / timed if timed > 0 else 0.0
         mean_loss = float(loss_hist[:n_loss].mean().item()) if n_loss else 0.0
         peak = torch.cuda.max_memory_allocated(device) if device.type == "cuda" else 0
         record = make_record(label, world, rank, args.seq_len, args.tier, args.steps,
                              args.per_device_batch, args.grad_accum, mean_step, mean_loss, peak)
         ev_times = [a.elapsed_time(b) / 1e3 for a, b in step_events] if step_events else []
-        tokens_step = args.per_device_batch * args.seq_len * world
+        tokens_step = tokens_per_micro_step(args.per_device_batch, args.seq_len, world, cp_n)
+        if cp_n > 1 and mean_step > 0:
+            # the record's formula counts per_device_batch * seq_len per rank; a context-parallel rank holds
+            # seq_len / N of its rows (the keys stay the reference's)
+            record["tokens_per_sec"] = tokens_step / mean_step
+            record["h2d_gbps_per_gpu"] = record["h2d_gbps_per_gpu"] / cp_n
         # a document mask depends on the data: count the table's visible pairs (window included), as the window
         # formula counts its band
         pairs = ds.visible_pairs_per_row(mcfg.sliding_window) if doc_len is not None else None
@@ -332,7 +384,12 @@ def train(args):
         tflops_gpu = (tokens_step / world) * flops_tok / mean_step / 1e12 if mean_step > 0 else 0.0
         extended = {
             "record_file_semantics": "tokens_per_sec = per_device_batch*seq_len*world_size / mean_step_time_sec "
-                                     "(reference formula; one micro-batch per step)",
+                                     "(reference formula; one micro-batch per step)"
+                                     + (f"; divided by context_parallel = {cp_n}: the ranks of a group share rows"
+                                        if cp_n > 1 else ""),
+            "context_parallel": cp_n, "cp_layout": cp_layout if cp_n > 1 else None,
+            "cp_ranges": (cp.describe(args.seq_len)["cp_ranges"] if cp is not None else None),
+            "tokens_per_micro_step": tokens_step,
             "timing": "barrier + device sync around the timed region; max over ranks (reference: rank-0 host "
                       "perf_counter without sync)",
             "wall_time_timed_sec": wall, "timed_steps": timed,
@@ -356,6 +413,7 @@ def train(args):
                                                   if timed > 0 and not (runner is not None and runner.graphs
                                                                         and not runner.disabled) else None),
             "comm_ops_timed": {k: dict(v) for k, v in engine.comm.stats.items()},
+            "cp_comm_ops_timed": cp_ops,
             "comm_topology": comm_describe(world) if (is_main and device.type == "cuda") else None,
             "fabric_calibration": fabric,
             "memory": engine.memory_report(),
@@ -400,6 +458,15 @@ def main(argv=None):
             parser.error(f"--eos-id must be in [0, {cfg0.vocab_size}) for tier {args.tier}")
     elif args.eos_id is not None:
         parser.error("--eos-id is only used together with --doc-len")
+    if args.context_parallel != 1:
+        cfg0 = get_model_config(args.tier, args.seq_len)
+        if args.sliding_window is not None:
+            cfg0.sliding_window = args.sliding_window
+        world0 = resolve_ranks(args.world_size, args.rank, args.local_rank)[0]
+        try:
+            check_context_parallel(args.context_parallel, args.cp_layout, world0, cfg0, args.seq_len)
+        except ValueError as e:
+            parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:
         args.deepspeed_config = default_config_path(args.strategy)
         print(f"[dltb] --deepspeed-config not given; using {args.deepspeed_config}", flush=True)

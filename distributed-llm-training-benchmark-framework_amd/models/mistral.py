@@ -87,6 +87,53 @@ class _EmbedFn(torch.autograd.Function):
         return None, None, None
 
 
+def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed):
+    """Context-parallel attention forward (parallel/context.py): RoPE with each range's positions, all-gather of
+    K | V into position order, then the range kernels -- the local queries of each range against all T keys.
+    ``qkv`` holds the local tokens range-major, so a range's rows are one block.  Returns (o, lse per range, kv)."""
+    cp = model.cp
+    B, T = model._cur_full_bt
+    rngs = cp.ranges(T)
+    n = qkv.shape[0] // len(rngs)
+    qd, kd = Hq * D, Hkv * D
+    cos, sin = model.rope(qkv.device, T)
+    for j, (c, s_) in enumerate(cp.rope_rows(cos, sin, T)):
+        F_.rope_(qkv[j * n:(j + 1) * n], c, s_, n // B, Hq + Hkv, D, False)
+    kv = cp.gather_kv(qkv[:, qd:], B, T)          # waits for the gather: the kernels below read it
+    o = torch.empty(qkv.shape[0], qd, dtype=qkv.dtype, device=qkv.device)
+    lses = []
+    for j, rng in enumerate(rngs):
+        _, lse, _ = F_.attn_fwd(qkv[j * n:(j + 1) * n, :qd], kv[:, :kd], kv[:, kd:], B, T, Hq, Hkv,
+                                1.0 / math.sqrt(D), True, 0.0, seed, 0, o_out=o[j * n:(j + 1) * n],
+                                window=window, bounds=bounds, q_range=rng)
+        lses.append(lse)
+    return o, lses, kv
+
+
+def _cp_attn_bwd(model, qkv, kv, o, do, lses, dqkv, Hq, Hkv, D, window, bounds, seed):
+    """The backward of :func:`_cp_attn_fwd`: dQ of each range into its rows of ``dqkv``; each range's dK | dV
+    over all T rows (zero where its queries see nothing), the zigzag pair summed by one add; reduce-scatter over
+    the group into the local K | V columns of ``dqkv``; then the inverse RoPE of the local rows as without
+    context parallelism."""
+    cp = model.cp
+    B, T = model._cur_full_bt
+    rngs = cp.ranges(T)
+    n = qkv.shape[0] // len(rngs)
+    qd, kd = Hq * D, Hkv * D
+    dkv = None
+    for j, rng in enumerate(rngs):
+        part = torch.empty_like(kv)
+        blk = slice(j * n, (j + 1) * n)
+        F_.attn_bwd(qkv[blk, :qd], kv[:, :kd], kv[:, kd:], o[blk], do[blk], lses[j], None, dqkv[blk, :qd],
+                    part[:, :kd], part[:, kd:], B, T, Hq, Hkv, 1.0 / math.sqrt(D), True, 0.0, seed, 0,
+                    window=window, bounds=bounds, q_range=rng)
+        dkv = part if dkv is None else dkv.add_(part)
+    cp.scatter_dkv(dkv, dqkv[:, qd:], B, T)       # waits for the reduce-scatter: the inverse RoPE reads it
+    cos, sin = model.rope(qkv.device, T)
+    for j, (c, s_) in enumerate(cp.rope_rows(cos, sin, T)):
+        F_.rope_(dqkv[j * n:(j + 1) * n], c, s_, n // B, Hq + Hkv, D, True)
+
+
 class _LayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, model, i):
@@ -95,16 +142,19 @@ class _LayerFn(torch.autograd.Function):
         cfg = model.cfg
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
-        cos, sin = model.rope(x.device, T)
         _, h1, _, rstd1 = F_.norm_fwd(x, None, w_in, None, cfg.norm_eps, True)
         qkv = F_.linear_fwd(h1, wqkv)
-        F_.rope_(qkv, cos, sin, T, Hq + Hkv, D, False)
         qd, kd = Hq * D, Hkv * D
         # document mask: the forward's bounds (window folded in) replace the window, and stay for the backward
         bounds = model._cur_bounds
         window = 0 if bounds is not None else cfg.sliding_window or 0
-        o, lse, aux = F_.attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
-                                  1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds)
+        if model.cp is not None:      # context parallel: local queries against the group's gathered K | V
+            o, lse, aux = _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, rt.seed)
+        else:
+            cos, sin = model.rope(x.device, T)
+            F_.rope_(qkv, cos, sin, T, Hq + Hkv, D, False)
+            o, lse, aux = F_.attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
+                                      1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds)
         a = F_.linear_fwd(o, wo)
         x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
         gu = F_.linear_fwd(h2, wgu)
@@ -127,7 +177,6 @@ class _LayerFn(torch.autograd.Function):
         cfg = model.cfg
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
-        cos, sin = model.rope(dx2.device, T)
         dx2 = dx2.contiguous()
         s = [rt.grad_slot(unit, j) for j in range(6)]
         F_.linear_wgrad(dx2, hh, s[5][0], None, s[5][1])
@@ -142,12 +191,16 @@ class _LayerFn(torch.autograd.Function):
         do = F_.linear_dgrad(dx1, wo, rt.weight_t(unit, 2, wo))
         qd, kd = Hq * D, Hkv * D
         dqkv = torch.empty_like(qkv)
-        F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
-                    dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
-                    1.0 / math.sqrt(D), True, 0.0, rt.seed, 0,
-                    window=0 if ctx.bounds is not None else cfg.sliding_window or 0, bounds=ctx.bounds)
+        window = 0 if ctx.bounds is not None else cfg.sliding_window or 0
+        if model.cp is not None:      # aux: the gathered K | V of the forward
+            _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed)
+        else:
+            cos, sin = model.rope(dx2.device, T)
+            F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
+                        dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
+                        1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds)
+            F_.rope_(dqkv, cos, sin, T, Hq + Hkv, D, True)      # RoPE is orthogonal: grad = R(-theta) g
         ctx.bounds = None
-        F_.rope_(dqkv, cos, sin, T, Hq + Hkv, D, True)      # RoPE is orthogonal: grad = R(-theta) g
         F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
         dh1 = F_.linear_dgrad(dqkv, wqkv, rt.weight_t(unit, 1, wqkv))
         dx = F_.norm_bwd(dh1, x, w_in, None, rstd1, dx1, s[0][0], None, s[0][1], True, red=red)
@@ -218,6 +271,7 @@ class MistralLM(nn.Module):
         self.rt = EAGER
         self.drop_p = 0.0
         self._rope = {}
+        self.cp = None          # parallel.context.ContextParallel.attach(): a layout, not a model property
         self.unit_embed = Unit("embed", [("model.embed_tokens.weight", self.model.embed_tokens.weight)], 0)
         self.unit_blocks = [Unit(f"layers.{i}", [(f"model.layers.{i}.{n}", p) for n, p in layer.param_list()], i + 1)
                             for i, layer in enumerate(self.model.layers)]
@@ -239,12 +293,21 @@ class MistralLM(nn.Module):
     def forward(self, idx, targets=None, return_logits=False):
         B, T = idx.shape
         assert T <= self.cfg.block_size
-        self._cur_bt = (B, T)
         # packed sequences: the document bounds of this batch, computed once (on the device, from idx, so a
         # captured step follows its static idx buffer) and shared by every layer's forward and backward
         self._cur_bounds = None
         if self.cfg.doc_eos_id is not None:
             self._cur_bounds = F_.doc_bounds(idx, self.cfg.doc_eos_id, self.cfg.sliding_window or 0)
+        if self.cp is not None:
+            # context parallel: every rank of the group got the same full rows (the bounds above are the full
+            # row's); from here on this rank holds its ranges' tokens only, range-major, as a batch of
+            # n_ranges * B shorter rows.  Targets equal inputs without a shift, so a slice carries its targets.
+            self._cur_full_bt = (B, T)
+            idx = self.cp.slice_rows(idx, T)
+            if targets is not None:
+                targets = self.cp.slice_rows(targets, T)
+            B, T = idx.shape
+        self._cur_bt = (B, T)
         anchor = torch.empty((), requires_grad=True)
         x = _EmbedFn.apply(anchor, idx, self)
         for i in range(len(self.unit_blocks)):

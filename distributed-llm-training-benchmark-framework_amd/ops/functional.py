@@ -483,40 +483,53 @@ def doc_bounds(idx, eos_id, window=0):
     return ref.doc_bounds(idx, int(eos_id), int(window or 0))
 
 
-def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, mask=None, o_out=None, window=0, bounds=None):
+def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, mask=None, o_out=None, window=0, bounds=None,
+             q_range=None):
     """Returns (o, lse, aux); ``aux`` (the packed dropout mask on the GPU) goes back into attn_bwd.
     ``window`` = W > 0 (causal only): query i sees keys ``i - W < j <= i``; 0 = no window.
     ``bounds`` (causal only, with ``window=0``): the document bounds of :func:`doc_bounds`; query i sees keys
-    ``bounds[0, b, i] <= j <= i``.  Hand-made bounds must keep its invariants: the kernels do not check them."""
+    ``bounds[0, b, i] <= j <= i``.  Hand-made bounds must keep its invariants: the kernels do not check them.
+    ``q_range`` = (q_begin, q_end), multiples of 128 (causal only, p = 0 unless it is (0, T)): q, o and lse hold
+    only those query rows of each batch row, k and v all T; masks, window and bounds keep meaning global
+    positions (:func:`ref.check_q_range`).  ``None`` or (0, T): the whole row, today's kernels."""
     ref.check_window(window, causal)
     ref.check_bounds(bounds, causal, window, B, T)
+    q_range = _q_range(q_range, T, causal, p)
     if _gpu(q):
         if p > 0 and mask is None:
             mask = ext().attn_mask(B, T, Hq, p, seed.device_tensor, site, q)
         o, lse = ext().attn_fwd(q, k, v, mask if p > 0 else None, B, T, Hq, Hkv, scale, causal, p, o_out,
-                                window, bounds)
+                                window, bounds, q_range)
         return o, lse, (mask if p > 0 else None)
-    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window, bounds)
+    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window, bounds, q_range)
     return _into(o_out, o), lse, None
 
 
+def _q_range(q_range, T, causal, p):
+    """The checked range, or None for the whole row (absent or (0, T): the square kernels, bit for bit)."""
+    qb, qe = ref.check_q_range(q_range, T, causal, p)
+    return None if (qb, qe) == (0, T) else (qb, qe)
+
+
 def attn_bwd(q, k, v, o, do, lse, aux, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0,
-             bounds=None):
+             bounds=None, q_range=None):
     """dQ (query-major kernel, which also forms delta = rowsum(dO * O) for its rows), then dK/dV
-    (key-major kernel, reading that delta).  ``window``, ``bounds``: as in :func:`attn_fwd`."""
+    (key-major kernel, reading that delta).  ``window``, ``bounds``, ``q_range``: as in :func:`attn_fwd`; with a
+    range dk / dv (all T rows) receive the range's contribution and zeros in every row none of its queries sees."""
     ref.check_window(window, causal)
     ref.check_bounds(bounds, causal, window, B, T)
+    q_range = _q_range(q_range, T, causal, p)
     if _gpu(q):
         C = ext()
         m = aux if p > 0 else None
         delta = torch.empty_like(lse)
         C.attn_bwd_part(1, q, k, v, do, lse, delta, m, dq, None, B, T, Hq, Hkv, scale, causal, p, o, window,
-                        bounds)
+                        bounds, q_range)
         C.attn_bwd_part(0, q, k, v, do, lse, delta, m, dk, dv, B, T, Hq, Hkv, scale, causal, p, None, window,
-                        bounds)
+                        bounds, q_range)
     else:
         ref.attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window,
-                     bounds)
+                     bounds, q_range)
 
 
 # ------------------------------------------------------------------------------ linear

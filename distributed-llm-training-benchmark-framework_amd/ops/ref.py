@@ -211,6 +211,32 @@ def check_bounds(bounds, causal, window, B, T):
         raise ValueError(f"attention: bounds must have shape [2, {B}, {T}], got {list(bounds.shape)}")
 
 
+Q_RANGE_ALIGN = 128      # the attention kernels' query block (csrc/attention.hip, kBlockRows)
+
+
+def check_q_range(q_range, T, causal, p):
+    """Query range ``(q_begin, q_end)`` of a length-``T`` problem: the query-side tensors (q, o, do, dq, lse) hold
+    only rows ``q_begin .. q_end - 1`` of every batch row, k / v / dk / dv all ``T`` rows, and every mask keeps
+    meaning global positions (tensor row i is position ``q_begin + i``).  Both ends are multiples of 128 with
+    ``0 <= q_begin < q_end <= T``; a range other than ``(0, T)`` is causal only and without attention dropout
+    (the packed keep-mask is laid out for the square problem).  ``None`` = the whole row.  Returns
+    ``(q_begin, q_end)``."""
+    if q_range is None:
+        return 0, T
+    qb, qe = int(q_range[0]), int(q_range[1])
+    if not 0 <= qb < qe <= T:
+        raise ValueError(f"attention: q_range must satisfy 0 <= begin < end <= T, got ({qb}, {qe}) with T = {T}")
+    if qb % Q_RANGE_ALIGN or qe % Q_RANGE_ALIGN:
+        raise ValueError(f"attention: q_range bounds must be multiples of {Q_RANGE_ALIGN}, got ({qb}, {qe})")
+    if (qb, qe) != (0, T):
+        if not causal:
+            raise ValueError("attention: a query range needs causal=True")
+        if p > 0:
+            raise ValueError("attention: a query range other than (0, T) needs dropout p = 0 (the packed keep-mask "
+                             "is laid out for the square problem)")
+    return qb, qe
+
+
 def doc_bounds(idx, eos_id, window=0):
     """Document mask of packed rows as two int32 planes ``[2, B, T]``.  A token equal to ``eos_id`` ends a
     document and belongs to it.  ``lo[b, i]`` is the first key query i sees (0 without an EOS in ``idx[b, :i]``,
@@ -236,10 +262,12 @@ def doc_bounds(idx, eos_id, window=0):
     return torch.stack([lo, hi]).to(torch.int32)
 
 
-def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0, bounds=None):
+def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0, bounds=None, qb=0, qe=None):
+    """Scores [B, Hq, Tq, T] of the queries at positions ``qb .. qe - 1`` (default: all T) against all T keys."""
     check_window(window, causal)
     check_bounds(bounds, causal, window, B, T)
-    qh = _f(q).reshape(B, T, Hq, D).transpose(1, 2)              # [B,Hq,T,D]
+    qe = T if qe is None else qe
+    qh = _f(q).reshape(B, qe - qb, Hq, D).transpose(1, 2)        # [B,Hq,Tq,D]
     kh = _f(k).reshape(B, T, Hkv, D).transpose(1, 2)
     if Hq != Hkv:
         kh = kh.repeat_interleave(Hq // Hkv, dim=1)
@@ -248,10 +276,11 @@ def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0, bounds=None):
         m = torch.ones(T, T, dtype=torch.bool, device=q.device).triu(1)
         if 0 < window < T:                                            # keys j <= i - W are out of the band
             m |= torch.ones(T, T, dtype=torch.bool, device=q.device).tril(-window)
-        s = s.masked_fill(m, float("-inf"))
+        s = s.masked_fill(m[qb:qe], float("-inf"))
         if bounds is not None:                                        # keys j < lo[b, i] are other documents
             j = torch.arange(T, device=q.device)
-            s = s.masked_fill((j[None, None, :] < bounds[0].to(q.device)[:, :, None])[:, None], float("-inf"))
+            lo = bounds[0].to(q.device)[:, qb:qe]                     # the lo plane is indexed by global query
+            s = s.masked_fill((j[None, None, :] < lo[:, :, None])[:, None], float("-inf"))
     return s
 
 
@@ -264,9 +293,12 @@ def _attn_keep(B, Hq, T, p, seed, site, device):
     return attn_keep_mask(s, rows, cols, p).view(B, Hq, T, T)
 
 
-def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0, bounds=None):
+def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0, bounds=None, q_range=None):
+    """``q_range`` (:func:`check_q_range`): q holds only the range's rows of each batch row; o [B * Tq, Hq * D]
+    and lse [B, Hq, Tq] come back for those rows."""
     D = q.shape[1] // Hq
-    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds)
+    qb, qe = check_q_range(q_range, T, causal, p)
+    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds, qb, qe)
     lse = torch.logsumexp(s, -1)                                      # [B,Hq,T]
     pr = torch.exp(s - lse[..., None])
     keep = _attn_keep(B, Hq, T, p, seed, site, q.device)
@@ -275,23 +307,27 @@ def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0, bou
     vh = _f(v).reshape(B, T, Hkv, D).transpose(1, 2)
     if Hq != Hkv:
         vh = vh.repeat_interleave(Hq // Hkv, dim=1)
-    o = torch.matmul(pr, vh).transpose(1, 2).reshape(B * T, Hq * D)
+    o = torch.matmul(pr, vh).transpose(1, 2).reshape(B * (qe - qb), Hq * D)
     return o.to(q.dtype), _f(lse).contiguous()
 
 
 def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0,
-             bounds=None):
+             bounds=None, q_range=None):
+    """``q_range``: q, o, do, lse, dq hold the range's rows; dk, dv all T rows -- the range's contribution, zero
+    in every row no query of the range sees."""
     D = q.shape[1] // Hq
     G = Hq // Hkv
-    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds)
-    pr = torch.exp(s - lse.view(B, Hq, T)[..., None])
+    qb, qe = check_q_range(q_range, T, causal, p)
+    Tq = qe - qb
+    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds, qb, qe)
+    pr = torch.exp(s - lse.view(B, Hq, Tq)[..., None])
     keep = _attn_keep(B, Hq, T, p, seed, site, q.device)
     z = torch.ones_like(pr) if keep is None else keep.to(pr.dtype) / (1.0 - p)   # fp64 inputs stay fp64
-    qh = _f(q).reshape(B, T, Hq, D).transpose(1, 2)
+    qh = _f(q).reshape(B, Tq, Hq, D).transpose(1, 2)
     kh = _f(k).reshape(B, T, Hkv, D).transpose(1, 2).repeat_interleave(G, dim=1)
     vh = _f(v).reshape(B, T, Hkv, D).transpose(1, 2).repeat_interleave(G, dim=1)
-    doh = _f(do).reshape(B, T, Hq, D).transpose(1, 2)
-    oh = _f(o).reshape(B, T, Hq, D).transpose(1, 2)
+    doh = _f(do).reshape(B, Tq, Hq, D).transpose(1, 2)
+    oh = _f(o).reshape(B, Tq, Hq, D).transpose(1, 2)
     delta = (doh * oh).sum(-1, keepdim=True)
     pd = pr * z
     dvh = torch.matmul(pd.transpose(-1, -2), doh)                     # [B,Hq,T,D]
@@ -302,7 +338,7 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, s
     if G > 1:
         dkh = dkh.view(B, Hkv, G, T, D).sum(2)
         dvh = dvh.view(B, Hkv, G, T, D).sum(2)
-    dq.copy_(dqh.transpose(1, 2).reshape(B * T, Hq * D).to(dq.dtype))
+    dq.copy_(dqh.transpose(1, 2).reshape(B * Tq, Hq * D).to(dq.dtype))
     dk.copy_(dkh.transpose(1, 2).reshape(B * T, Hkv * D).to(dk.dtype))
     dv.copy_(dvh.transpose(1, 2).reshape(B * T, Hkv * D).to(dv.dtype))
 

@@ -4,6 +4,8 @@
     python scripts/bench_attn.py [--iters 50]
     python scripts/bench_attn.py --window 4096 --seq-lens 8192,16384,32768   # sliding window vs full causal
     python scripts/bench_attn.py --doc-len 2048 [--window 4096]              # packed documents vs full causal
+    python scripts/bench_attn.py --cp 8 --cp-layout zigzag [--window 4096]   # every rank's query ranges vs the whole row
+    python scripts/bench_attn.py --q-range 0:2048 --q-range 30720:32768 --seq-lens 32768
 
 Prints one line per kernel: time per call and TFLOP/s (causal FLOPs counted over the visible
 half).  Shapes: TinyGPT-A (B1 T2048 H16 D64, dropout 0.1, non-causal) and Mistral-7B
@@ -14,6 +16,12 @@ with the window (query i sees keys i - W < j <= i) and without it, in one proces
 alternate over ``--rounds`` rounds of ``--iters`` calls (after a warm-up round), and the median round is
 reported with the min .. max spread, next to the ratio of visited 64-key tiles (window / causal) that the
 kernels' tile bounds give.
+
+``--q-range B:E`` (repeatable; ``--cp N --cp-layout L`` is shorthand for the ranges of every rank of a
+context-parallel group, dltb/parallel/context.py) times the three passes of each query range of the Mistral-7B
+attention shape next to the whole-row call at the same ``--seq-lens`` length (and ``--window``), all alternating in
+one process as above, with the ratio of visited tiles (range / whole row).  With ``--cp`` it also prints every
+rank's summed time and the max / mean ratio over the ranks: the balance of the attention kernels of one step.
 """
 import argparse
 import json
@@ -138,6 +146,81 @@ def run_window(T, W, iters, rounds, B=1, Hq=32, Hkv=8, D=128, p=0.0):
     return out
 
 
+def range_tile_counts(T, W, qb, qe):
+    """tile_counts for the query range [qb, qe): the query-major kernels visit the range's blocks only, every key
+    block of the key-major kernel walks the range's query tiles only."""
+    qmaj = kmaj = 0
+    for blk in range(T // 128):
+        if qb <= blk * 128 < qe:
+            hi = min(T // 64, (blk * 128 + 127) // 64 + 1)
+            qmaj += hi - (max(0, blk * 128 - W + 1) // 64 if W else 0)
+        end = min(T // 64, (blk * 128 + 127 + W - 1) // 64 + 1) if W else T // 64
+        kmaj += max(0, min(end, qe // 64) - max(blk * 128 // 64, qb // 64))
+    return qmaj, kmaj
+
+
+def run_qrange(T, W, ranges, iters, rounds, B=1, Hq=32, Hkv=8, D=128, ranks=None):
+    """Forward, dQ and dK/dV of every query range in ``ranges`` next to the whole-row call (window ``W`` or full
+    causal), alternating as in run_window.  ``ranks``: {rank: [ranges]} for the per-rank sums of ``--cp``."""
+    C = ext()
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    qkv = torch.randn(B * T, (Hq + 2 * Hkv) * D, device=dev, dtype=torch.bfloat16, generator=g)
+    q, k, v = qkv[:, :Hq * D], qkv[:, Hq * D:(Hq + Hkv) * D], qkv[:, (Hq + Hkv) * D:]
+    do = torch.randn(B * T, Hq * D, device=dev, dtype=torch.bfloat16, generator=g)
+    scale = D ** -0.5
+    dkv = torch.empty(B * T, 2 * Hkv * D, device=dev, dtype=torch.bfloat16)
+    dk, dv = dkv[:, :Hkv * D], dkv[:, Hkv * D:]
+    fns = {}
+    for rng in [None] + list(ranges):
+        qb, qe = rng or (0, T)
+        kw = {"window": W} if rng is None else {"window": W, "q_range": rng}
+        ql = q.view(B, T, -1)[:, qb:qe].reshape(B * (qe - qb), -1).contiguous()
+        dol = do.view(B, T, -1)[:, qb:qe].reshape(B * (qe - qb), -1).contiguous()
+        o, lse = C.attn_fwd(ql, k, v, None, B, T, Hq, Hkv, scale, True, 0.0, **kw)
+        delta = C.attn_bwd_delta(o, dol, B, qe - qb, Hq)
+        dq = torch.empty_like(ql)
+        fns["fwd", rng] = lambda ql=ql, kw=kw: C.attn_fwd(ql, k, v, None, B, T, Hq, Hkv, scale, True, 0.0, **kw)
+        fns["dq", rng] = lambda ql=ql, dol=dol, lse=lse, delta=delta, dq=dq, kw=kw: C.attn_bwd_part(
+            1, ql, k, v, dol, lse, delta, None, dq, None, B, T, Hq, Hkv, scale, True, 0.0, **kw)
+        fns["dkdv", rng] = lambda ql=ql, dol=dol, lse=lse, delta=delta, kw=kw: C.attn_bwd_part(
+            0, ql, k, v, dol, lse, delta, None, dk, dv, B, T, Hq, Hkv, scale, True, 0.0, **kw)
+    times = {key: [] for key in fns}
+    for r in range(rounds + 1):                 # round 0 warms up; whole-row and range calls alternate
+        for key, fn in fns.items():
+            us = timeit(fn, iters)
+            if r:
+                times[key].append(us)
+    med = {key: sorted(t)[len(t) // 2] for key, t in times.items()}
+    full = tile_counts(T, W)
+    out = {"full": {kn: med[kn, None] for kn in ("fwd", "dq", "dkdv")}, "ranges": {}}
+    print(f"T {T:6d} W {W:5d} whole row: " + "  ".join(
+        f"{kn} {med[kn, None]:9.1f} us ({min(times[kn, None]):.1f} .. {max(times[kn, None]):.1f})"
+        for kn in ("fwd", "dq", "dkdv")), flush=True)
+    for rng in ranges:
+        tc = range_tile_counts(T, W, *rng)
+        rec = {}
+        for kn, tiles in (("fwd", tc[0] / full[0]), ("dq", tc[0] / full[0]), ("dkdv", tc[1] / full[1])):
+            m, f = med[kn, rng], med[kn, None]
+            rec[kn] = dict(us=m, full_us=f, time_ratio=m / f, tile_ratio=tiles)
+            print(f"T {T:6d} W {W:5d} range {rng[0]:6d}:{rng[1]:<6d} {kn:5s} {m:9.1f} us "
+                  f"({min(times[kn, rng]):.1f} .. {max(times[kn, rng]):.1f})  time ratio {m / f:.3f}  "
+                  f"tile ratio {tiles:.3f}" + ("" if m <= f else "  SLOWER THAN THE WHOLE ROW"), flush=True)
+        out["ranges"][f"{rng[0]}:{rng[1]}"] = rec
+    if ranks:
+        tot = {r: sum(med[kn, rng] for rng in rr for kn in ("fwd", "dq", "dkdv")) for r, rr in ranks.items()}
+        mean = sum(tot.values()) / len(tot)
+        for r, t in tot.items():
+            print(f"T {T:6d} W {W:5d} rank {r}: ranges {ranks[r]}  fwd + dq + dkdv {t:9.1f} us", flush=True)
+        whole = sum(med[kn, None] for kn in ("fwd", "dq", "dkdv"))
+        print(f"T {T:6d} W {W:5d} over {len(tot)} ranks: max {max(tot.values()):.1f} us, mean {mean:.1f} us, "
+              f"max / mean {max(tot.values()) / mean:.3f}; whole row on one GPU {whole:.1f} us "
+              f"(whole / max {whole / max(tot.values()):.2f})", flush=True)
+        out["ranks"] = {str(r): t for r, t in tot.items()}
+        out["max_over_mean"] = max(tot.values()) / mean
+    return out
+
+
 def doc_tile_counts(bounds, T):
     """tile_counts for document bounds [2, 1, T] (CPU): the tile ranges of the bounds kernels."""
     lo, hi = bounds[0, 0].tolist(), bounds[1, 0].tolist()
@@ -211,8 +294,23 @@ def main():
                     help="compare document-masked attention (packed documents of this mean length, one seeded "
                          "layout; composes with --window) with full causal attention at --seq-lens")
     ap.add_argument("--dropout", type=float, default=0.0, help="attention dropout of the --doc-len comparison")
+    ap.add_argument("--q-range", action="append", default=[], metavar="B:E",
+                    help="time this query range (multiples of 128) next to the whole row at --seq-lens; repeatable")
+    ap.add_argument("--cp", type=int, default=0, help="shorthand: the query ranges of every rank of a group of N")
+    ap.add_argument("--cp-layout", default="auto", choices=["auto", "contiguous", "zigzag"])
     a = ap.parse_args()
-    if a.doc_len > 0:
+    if a.q_range or a.cp > 1:
+        from dltb.parallel import context as cpx
+        out = {}
+        for T in (int(x) for x in a.seq_lens.split(",")):
+            ranges, ranks = [tuple(int(x) for x in r.split(":")) for r in a.q_range], None
+            if a.cp > 1:
+                layout = cpx.resolve_layout(a.cp_layout, a.window)
+                ranks = {r: cpx.ranges(layout, T, a.cp, r) for r in range(a.cp)}
+                ranges += [rng for rr in ranks.values() for rng in rr if rng not in ranges]
+            out[f"T{T}_W{a.window}_cp{a.cp}_{a.cp_layout}"] = run_qrange(T, a.window, ranges, a.iters, a.rounds,
+                                                                        ranks=ranks)
+    elif a.doc_len > 0:
         out = {f"T{T}_N{a.doc_len}_W{a.window}": run_docs(T, a.doc_len, a.window, a.iters, a.rounds, p=a.dropout)
                for T in (int(x) for x in a.seq_lens.split(","))}
     elif a.window > 0:

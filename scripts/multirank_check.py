@@ -20,7 +20,10 @@ vocab 8192) under ZeRO-3 -- BASELINE config #5's shapes through every sharded co
 no weight decay, which makes an update ~ lr * gradient (not the sign of it), so comparing the
 parameter *updates* of two runs compares their reduced gradients.  Rank 0 writes
 {case: {"init", "final", "losses"}} (fp32, CPU) to ``--out``; tests/test_multirank_gpu.py compares
-the two files.  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
+the two files.  ``--context-parallel N`` (with ``--cp-layout``) splits every row over groups of N consecutive
+ranks (dltb/parallel/context.py): the ranks of a group read the same rows, and the run must train the model the
+world-1 run trains.  Its Mistral-shape cases (``CP_CASES``: every strategy, a sliding window, packed documents)
+are not part of the default ``--cases``.  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
 DeepSpeed ZeRO-2/3 wrap) -- at any world size the trained model must be the one the global batch
 defines.
 """
@@ -61,6 +64,17 @@ EXTRA_CASES = {
 }
 
 
+# context parallelism needs the causal Mistral shape; run with --context-parallel N (N = 1: the reference run)
+CP_CASES = {
+    "cp_ddp": dict(strategy="ddp", tier="mtiny"),
+    "cp_fsdp": dict(strategy="fsdp", tier="mtiny"),
+    "cp_zero2": dict(strategy="zero2", tier="mtiny"),
+    "cp_zero3": dict(strategy="zero3", tier="mtiny", persist=1024),
+    "cp_zero3_window": dict(strategy="zero3", tier="mtiny", persist=1024, window=96),
+    "cp_zero2_doc": dict(strategy="zero2", tier="mtiny", doc_len=96),
+}
+
+
 def model_config(tier, seq_len, dropout=0.0):
     from dltb.models import get_model_config
     if tier == "mtiny":
@@ -81,8 +95,18 @@ def run_case(name, spec, world, rank, device, a):
     mcfg = model_config(spec.get("tier", "A"), a.seq_len, spec.get("dropout", 0.0))
     if "layers" in spec:
         mcfg.n_layer = int(spec["layers"])
+    if spec.get("window"):
+        mcfg.sliding_window = int(spec["window"])
+    if spec.get("doc_len"):
+        mcfg.doc_eos_id = mcfg.vocab_size - 1
+    if spec.get("window") or spec.get("doc_len"):
+        mcfg.validate()
     with torch.device(device):
         model = build_model(mcfg)
+    cp = a.context_parallel
+    if cp > 1:
+        from dltb.parallel.context import ContextParallel
+        ContextParallel(cp, a.cp_layout, mcfg.sliding_window).attach(model)
     init = {n: p.detach().float().cpu().clone() for n, p in model.named_parameters()}
     fc = None
     if spec["strategy"] == "fsdp":
@@ -102,12 +126,18 @@ def run_case(name, spec, world, rank, device, a):
     g = torch.Generator().manual_seed(123)
     steps = a.windows * a.accum
     table = torch.randint(0, mcfg.vocab_size, (steps, a.ref_batch, a.seq_len), generator=g)
-    per = a.ref_batch // world
+    if spec.get("doc_len"):          # documents of mean length doc_len: an EOS after every token with p = 1 / doc_len
+        ends = torch.rand(table.shape, generator=g) < 1.0 / spec["doc_len"]
+        table = torch.where(ends, torch.full_like(table, mcfg.doc_eos_id), table)
+    # the ranks of a context-parallel group read the same rows: the rows are dealt to the groups
+    groups, rank_rows = world // cp, rank // cp
+    assert a.ref_batch % groups == 0
+    per = a.ref_batch // groups
     same = spec.get("same_rows", False)
     losses, rank_losses = [], []
     for k in range(steps):
         # same_rows: every rank (and every row of the world-1 batch) reads row 0 of the micro-step
-        b = (table[k, :1].expand(per, -1).contiguous() if same else table[k, rank * per:(rank + 1) * per]).to(device)
+        b = (table[k, :1].expand(per, -1).contiguous() if same else table[k, rank_rows * per:(rank_rows + 1) * per]).to(device)
         loss = eng(b, b)[1]
         eng.backward(loss)
         eng.step()
@@ -136,17 +166,19 @@ def main():
     ap.add_argument("--lr", type=float, default=0.05)
     ap.add_argument("--bucket-mb", type=float, default=1.0, help="small buckets: several per model")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--context-parallel", type=int, default=1, help="ranks per context-parallel group")
+    ap.add_argument("--cp-layout", default="auto", choices=["auto", "contiguous", "zigzag"])
     a = ap.parse_args()
     from dltb.utils.dist import cleanup_distributed, setup_distributed
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    assert a.ref_batch % world == 0
+    assert world % a.context_parallel == 0 and a.ref_batch % (world // a.context_parallel) == 0
     device = setup_distributed(world, rank, local, device_type=a.device, timeout_min=5)
     out = {}
     try:
         for name in a.cases.split(","):
-            out[name] = run_case(name, {**CASES, **EXTRA_CASES}[name], world, rank, device, a)
+            out[name] = run_case(name, {**CASES, **EXTRA_CASES, **CP_CASES}[name], world, rank, device, a)
             if rank == 0:
                 print(f"[multirank_check] ws={world} {name}: losses {['%.4f' % v for v in out[name]['losses']]}",
                       flush=True)
