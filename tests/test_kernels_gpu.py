@@ -464,8 +464,8 @@ def test_adamw_matches_torch(gdtype):
 
 def test_adamw_mixed_alignment_segments():
     """FlatAdamW over two segments, the second neither 8-element aligned in the owner space nor 16-byte
-    aligned at its destination: its blocks take the 8-byte path, the first segment's the 16-byte path;
-    both match torch.optim.AdamW."""
+    aligned at its destination (the kernel moves the 16-bit copies in 8-byte accesses, 4 elements per
+    lane, whatever the alignment); both match torch.optim.AdamW."""
     from dltb.optim.adamw import FlatAdamW
     n, cut = 100_000, 50_004
     p0 = torch.randn(n, device=DEV)
