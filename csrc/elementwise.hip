@@ -7,6 +7,7 @@
 //   dropout_add         out = x + dropout(r)                              (residual + Dropout)
 //   dropout_bwd         out = dropout_mask(g) * 1/(1-p)                   (mask regenerated)
 //   swiglu_fwd/bwd      h = silu(gate) * up                               (Mistral-shape FFN)
+//   swiglu_bwd_h        swiglu_bwd that also rebuilds h                   (activation recomputation)
 //   rope_fwd/bwd        rotate-half RoPE in place on the q/k columns of a fused qkv buffer
 //   f32_from_bf16       dst (+)= float(src)
 //   transpose           dst[C, R] = src[R, C]^T (64x64 LDS tiles; cached W^T for dgrad GEMMs)
@@ -204,6 +205,36 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* __restric
   }
 }
 
+// swiglu_bwd that also rebuilds h = silu(gate) * up (activation recomputation: the forward did not keep h):
+// gate | up and dh are read once for both outputs, instead of a swiglu_fwd launch re-reading gu.  The
+// expressions are the two kernels' above, so h is bitwise swiglu_fwd's and dgu bitwise swiglu_bwd's.
+__global__ __launch_bounds__(256) void swiglu_bwd_h_kernel(const bf16_t* __restrict__ dh,
+                                                          const bf16_t* __restrict__ gu,
+                                                          bf16_t* __restrict__ dgu, bf16_t* __restrict__ h,
+                                                          int N, int F) {
+  const long n8 = (long)N * F / 8;
+  const int fv = F >> 3;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / fv;
+    const long c = (i - row * fv) * 8;
+    float g[8], u[8], d[8], dg[8], du[8], o[8];
+    unpack8(ld16<uint4>(gu + row * 2 * F + c), g);
+    unpack8(ld16<uint4>(gu + row * 2 * F + F + c), u);
+    unpack8(ld16<uint4>(dh + row * F + c), d);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float s = sigmoid_f(g[e]);
+      const float silu = g[e] * s;
+      o[e] = silu * u[e];
+      du[e] = d[e] * silu;
+      dg[e] = d[e] * u[e] * s * (1.f + g[e] * (1.f - s));
+    }
+    *reinterpret_cast<uint4*>(h + row * F + c) = pack8(o);
+    *reinterpret_cast<uint4*>(dgu + row * 2 * F + c) = pack8(dg);
+    *reinterpret_cast<uint4*>(dgu + row * 2 * F + F + c) = pack8(du);
+  }
+}
+
 // ------------------------------------------------------------------------------- RoPE
 // qkv rows of width `stride`; q heads [0, Hq*D), k heads [Hq*D, (Hq+Hkv)*D).  cos/sin: [T, D/2]
 // fp32 host-built tables.  Each thread rotates 8 consecutive pairs (i, i + D/2) of one head.
@@ -394,6 +425,11 @@ void dltb_swiglu_fwd(const void* gu, void* h, int N, int F, hipStream_t st) {
 void dltb_swiglu_bwd(const void* dh, const void* gu, void* dgu, int N, int F, hipStream_t st) {
   hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(ew_grid((long)N * F / 8)), dim3(256), 0, st,
                      (const bf16_t*)dh, (const bf16_t*)gu, (bf16_t*)dgu, N, F);
+}
+
+void dltb_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, int N, int F, hipStream_t st) {
+  hipLaunchKernelGGL(swiglu_bwd_h_kernel, dim3(ew_grid((long)N * F / 8)), dim3(256), 0, st,
+                     (const bf16_t*)dh, (const bf16_t*)gu, (bf16_t*)dgu, (bf16_t*)h, N, F);
 }
 
 void dltb_rope(void* qkv, const float* cosb, const float* sinb, int N, int T, int heads, int D,

@@ -9,6 +9,9 @@ void dltb_norm_fwd(const void* x, const void* r, const void* w, const void* b, v
                    void* y, float* mean, float* rstd, int N, int d, float eps, bool rms,
                    uint32_t thr16, float drop_scale, const int64_t* seed, int64_t site,
                    hipStream_t st);
+// y = norm_fwd's y rebuilt from the row statistics norm_fwd wrote (no row reduction); ys: y's row stride
+void dltb_norm_apply(const void* s, const void* w, const void* b, const float* mean, const float* rstd,
+                     void* y, long ys, int N, int d, bool rms, hipStream_t st);
 // norm_fwd + the attention-dropout mask of (B, T, Hq) in one launch (horizontal fusion)
 void dltb_norm_fwd_mask(const void* x, const void* r, const void* w, const void* b, void* s_out, void* y,
                         float* mean, float* rstd, int N, int d, float eps, bool rms, uint32_t thr16,
@@ -46,6 +49,8 @@ void dltb_dropout(const void* x, const void* r, void* out, long n, int cols, uin
                   float scale, const int64_t* seed, int64_t site, hipStream_t st);
 void dltb_swiglu_fwd(const void* gu, void* h, int N, int F, hipStream_t st);
 void dltb_swiglu_bwd(const void* dh, const void* gu, void* dgu, int N, int F, hipStream_t st);
+// swiglu_bwd plus h = swiglu_fwd(gu) rebuilt in the same pass (activation recomputation)
+void dltb_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, int N, int F, hipStream_t st);
 void dltb_rope(void* qkv, const float* cosb, const float* sinb, int N, int T, int heads, int D,
                int stride, bool inverse, hipStream_t st);
 void dltb_f32_from_bf16(float* dst, const void* src, long n, int accumulate, hipStream_t st);

@@ -5,6 +5,8 @@
 //     y = (s - mean) * rstd * w + b          (LayerNorm)   |   y = s * rstd * w   (RMSNorm)
 // One 64-lane wave per row, the row held in registers as 16-byte bf16x8 vectors, fp32 stats.
 //
+// norm_apply rebuilds y from s and the saved mean / rstd in one streaming pass (activation recomputation).
+//
 // Backward: one wave per row computes dx (+ the incoming residual gradient) and accumulates
 // per-column dgamma/dbeta partials; a block folds its 4 waves through LDS float atomics and
 // writes one fp32 partial row; `norm_colreduce` sums the partials into the bf16 gradient slot
@@ -153,6 +155,38 @@ __global__ __launch_bounds__(256) void norm_fwd_mask_kernel(
     const int m = bid - nb_norm;
     attn_mask_word(mj.mask, mj.T, mj.thr16, mj.seed, mj.site, (m % mj.gx) * 256 + threadIdx.x,
                    (uint32_t)(mj.g0 + m / mj.gx));
+  }
+}
+
+// y of norm_fwd rebuilt from s and the row statistics norm_fwd wrote (activation recomputation: the forward
+// did not keep y).  No row reduction, so no wave-per-row shape: a grid-stride stream over the N * d / 8
+// 16-byte vectors; the per-row statistics and w / b come from L1 / L2.  The element expressions are
+// norm_fwd_row's on the same fp32 inputs (s is the stored, rounded residual stream either way), so y is bitwise
+// norm_fwd's.  ys: row stride of y in elements.
+template <bool RMS>
+__global__ __launch_bounds__(256) void norm_apply_kernel(
+    const bf16_t* __restrict__ s, const bf16_t* __restrict__ w, const bf16_t* __restrict__ b,
+    const float* __restrict__ mean_in, const float* __restrict__ rstd_in, bf16_t* __restrict__ y, long ys,
+    long n8, int d) {
+  const int nvec = d >> 3;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / nvec;
+    const int c = (int)(i - row * nvec) * 8;
+    const float rstd = rstd_in[row];
+    float v[8], wv[8], o[8];
+    unpack8(ld16<uint4>(s + row * d + c), v);
+    unpack8(ld16<uint4>(w + c), wv);
+    if (!RMS) {
+      const float mean = mean_in[row];
+      float bv[8];
+      unpack8(ld16<uint4>(b + c), bv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = (v[e] - mean) * rstd * wv[e] + bv[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = v[e] * rstd * wv[e];
+    }
+    *reinterpret_cast<uint4*>(y + row * ys + c) = pack8(o);
   }
 }
 
@@ -497,6 +531,20 @@ void dltb_norm_fwd(const void* x, const void* r, const void* w, const void* b, v
     if (r) launch_fwd_t<false, true>(nv, grid, st, X, R, W, B, S, Y, mean, rstd, N, d, eps, thr16, drop_scale, seed, site);
     else   launch_fwd_t<false, false>(nv, grid, st, X, R, W, B, S, Y, mean, rstd, N, d, eps, thr16, drop_scale, seed, site);
   }
+}
+
+void dltb_norm_apply(const void* s, const void* w, const void* b, const float* mean, const float* rstd,
+                     void* y, long ys, int N, int d, bool rms, hipStream_t st) {
+  const long n8 = (long)N * d / 8;
+  long grid = (n8 + 255) / 256;
+  if (grid > 2048) grid = 2048;
+  if (grid < 1) grid = 1;
+  if (rms)
+    hipLaunchKernelGGL(norm_apply_kernel<true>, dim3(grid), dim3(256), 0, st, (const bf16_t*)s, (const bf16_t*)w,
+                       (const bf16_t*)b, mean, rstd, (bf16_t*)y, ys, n8, d);
+  else
+    hipLaunchKernelGGL(norm_apply_kernel<false>, dim3(grid), dim3(256), 0, st, (const bf16_t*)s, (const bf16_t*)w,
+                       (const bf16_t*)b, mean, rstd, (bf16_t*)y, ys, n8, d);
 }
 
 template <bool RMS, bool HAS_RES>

@@ -14,7 +14,7 @@ Differences that make the numbers honest (recorded in the extended sidecar):
 * per-step losses stay on the device and are read once at the end (the reference syncs every step).
 Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device, --bucket-mb, --dropout, --seed,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
---doc-len, --context-parallel, --cp-layout.
+--doc-len, --context-parallel, --cp-layout, --activation-recompute.
 """
 import argparse
 import json
@@ -73,6 +73,12 @@ def build_parser():
     p.add_argument("--cp-layout", choices=["auto", "contiguous", "zigzag"], default="auto",
                    help="which tokens a rank of a context-parallel group owns; auto: zigzag (balanced causal work) "
                         "without --sliding-window, contiguous with it")
+    p.add_argument("--activation-recompute", choices=["off", "selective", "full"], default="off",
+                   help="causal tiers: what a layer's forward keeps for its backward.  selective drops the two norm "
+                        "outputs and the SwiGLU output (-32 %% of the saved activations; rebuilt by elementwise "
+                        "kernels); full keeps only the layer input and the attention output (-88 %%) and re-runs "
+                        "the qkv, o and gate|up projections in the backward (about a quarter more GEMM work per "
+                        "step); attention itself is never re-run")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -174,6 +180,13 @@ def check_context_parallel(cp, layout, world, mcfg, seq_len):
     return layout
 
 
+def check_activation_recompute(mode, mcfg, tier):
+    """ValueError when ``--activation-recompute`` is set for a tier whose layers cannot drop activations."""
+    if mode != "off" and not mcfg.causal:
+        raise ValueError(f"--activation-recompute needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} keeps "
+                         "its activations in layer-strided buffers that its window-wide weight-gradient queue reads")
+
+
 def train(args):
     world, rank, local_rank = resolve_ranks(args.world_size, args.rank, args.local_rank)
     args.world_size, args.rank, args.local_rank = world, rank, local_rank
@@ -232,8 +245,14 @@ def train(args):
             mcfg.doc_eos_id = eos_id
             mcfg.validate()
         cp_layout = check_context_parallel(cp_n, getattr(args, "cp_layout", "auto"), world, mcfg, args.seq_len)
+        recompute = getattr(args, "activation_recompute", None) or "off"
+        check_activation_recompute(recompute, mcfg, args.tier)
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
+        if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
+            model.activation_recompute = recompute
+            if is_main:
+                print(f"Activation recompute: {recompute}", flush=True)
         cp = None
         if cp_n > 1:
             cp = _context.ContextParallel(cp_n, cp_layout, mcfg.sliding_window, world, rank)
@@ -388,6 +407,7 @@ def train(args):
                                      + (f"; divided by context_parallel = {cp_n}: the ranks of a group share rows"
                                         if cp_n > 1 else ""),
             "context_parallel": cp_n, "cp_layout": cp_layout if cp_n > 1 else None,
+            "activation_recompute": recompute,
             "cp_ranges": (cp.describe(args.seq_len)["cp_ranges"] if cp is not None else None),
             "tokens_per_micro_step": tokens_step,
             "timing": "barrier + device sync around the timed region; max over ranks (reference: rank-0 host "
@@ -467,6 +487,10 @@ def main(argv=None):
             check_context_parallel(args.context_parallel, args.cp_layout, world0, cfg0, args.seq_len)
         except ValueError as e:
             parser.error(str(e))
+    try:
+        check_activation_recompute(args.activation_recompute, get_model_config(args.tier, args.seq_len), args.tier)
+    except ValueError as e:
+        parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:
         args.deepspeed_config = default_config_path(args.strategy)
         print(f"[dltb] --deepspeed-config not given; using {args.deepspeed_config}", flush=True)

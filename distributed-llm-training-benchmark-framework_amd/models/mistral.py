@@ -87,6 +87,19 @@ class _EmbedFn(torch.autograd.Function):
         return None, None, None
 
 
+def _cp_rope_gather(model, qkv, Hq, Hkv, D):
+    """The part of the context-parallel attention forward before its kernels: RoPE in place with each range's
+    positions, then the all-gather of K | V into position order.  Returns kv.  Also the backward's re-gather
+    under ``activation_recompute = "full"``, which does not keep kv."""
+    cp = model.cp
+    B, T = model._cur_full_bt
+    n = qkv.shape[0] // len(cp.ranges(T))
+    cos, sin = model.rope(qkv.device, T)
+    for j, (c, s_) in enumerate(cp.rope_rows(cos, sin, T)):
+        F_.rope_(qkv[j * n:(j + 1) * n], c, s_, n // B, Hq + Hkv, D, False)
+    return cp.gather_kv(qkv[:, Hq * D:], B, T)    # waits for the gather: the kernels read it
+
+
 def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed):
     """Context-parallel attention forward (parallel/context.py): RoPE with each range's positions, all-gather of
     K | V into position order, then the range kernels -- the local queries of each range against all T keys.
@@ -96,10 +109,7 @@ def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed):
     rngs = cp.ranges(T)
     n = qkv.shape[0] // len(rngs)
     qd, kd = Hq * D, Hkv * D
-    cos, sin = model.rope(qkv.device, T)
-    for j, (c, s_) in enumerate(cp.rope_rows(cos, sin, T)):
-        F_.rope_(qkv[j * n:(j + 1) * n], c, s_, n // B, Hq + Hkv, D, False)
-    kv = cp.gather_kv(qkv[:, qd:], B, T)          # waits for the gather: the kernels below read it
+    kv = _cp_rope_gather(model, qkv, Hq, Hkv, D)
     o = torch.empty(qkv.shape[0], qd, dtype=qkv.dtype, device=qkv.device)
     lses = []
     for j, rng in enumerate(rngs):
@@ -164,11 +174,18 @@ class _LayerFn(torch.autograd.Function):
         rt.release_forward(unit)
         ctx.model, ctx.i = model, i
         ctx.saved = (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh)
+        ctx.recompute = _check_recompute(model.activation_recompute)
+        if ctx.recompute == "selective":      # the backward rebuilds h1, h2 (norm_apply) and hh (swiglu_bwd_h)
+            ctx.saved = (x, None, rstd1, qkv, o, lse, aux, x1, None, rstd2, gu, None)
+        elif ctx.recompute == "full":         # ... and everything else but the attention output
+            ctx.saved = (x, None, None, None, o, lse, None, None, None, None, None, None)
         ctx.bounds = bounds
         return x2
 
     @staticmethod
     def backward(ctx, dx2):
+        if ctx.recompute != "off":
+            return _layer_backward_recompute(ctx, dx2), None, None
         model, i = ctx.model, ctx.i
         rt, unit = model.rt, model.unit_blocks[i]
         (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh) = ctx.saved
@@ -209,6 +226,98 @@ class _LayerFn(torch.autograd.Function):
         rt.grads_ready(unit)
         rt.release_backward(unit)
         return dx, None, None
+
+
+RECOMPUTE_MODES = ("off", "selective", "full")
+
+
+def _check_recompute(mode):
+    if mode not in RECOMPUTE_MODES:
+        raise ValueError(f"activation_recompute must be one of {', '.join(RECOMPUTE_MODES)}, got {mode!r}")
+    return mode
+
+
+def _layer_backward_recompute(ctx, dx2):
+    """:meth:`_LayerFn.backward` for a forward that kept a reduced set (``model.activation_recompute``):
+
+    * ``selective`` kept everything but the norm outputs h1, h2 and the SwiGLU output hh; they come back from
+      elementwise kernels (``norm_apply`` from the kept row statistics, ``swiglu_bwd_h`` inside the SwiGLU backward).
+    * ``full`` kept x, o, lse.  The MLP half (a = o Wo^T, x1 / h2 / rstd2, gu) is rebuilt first and the attention
+      half (h1 / rstd1, qkv + RoPE, under context parallelism the gathered K | V) only when the MLP half has been
+      consumed and freed, so the rebuilt working set is half a layer's.  Attention itself and the down projection
+      are not re-run.
+
+    Every rebuilt tensor is the forward's bit for bit (same kernels on the same inputs; hash-seeded randomness),
+    the gradient kernels are ``off``'s with ``swiglu_bwd`` replaced by ``swiglu_bwd_h`` (the wd weight gradient
+    moves behind it), and each tensor is dropped after its last consumer."""
+    model, i = ctx.model, ctx.i
+    full = ctx.recompute == "full"
+    rt, unit = model.rt, model.unit_blocks[i]
+    (x, _, rstd1, qkv, o, lse, aux, x1, _, rstd2, gu, _) = ctx.saved
+    ctx.saved = None
+    (w_in, wqkv, wo, w_post, wgu, wd) = rt.acquire_backward(unit)
+    cfg = model.cfg
+    B, T = model._cur_bt
+    Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
+    qd, kd = Hq * D, Hkv * D
+    dx2 = dx2.contiguous()
+    s = [rt.grad_slot(unit, j) for j in range(6)]
+    # ---- MLP half
+    if full:
+        a = F_.linear_fwd(o, wo)
+        x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
+        del a
+        gu = F_.linear_fwd(h2, wgu)
+    else:
+        h2 = F_.norm_apply(x1, w_post, None, None, rstd2, True)
+    dhh = F_.linear_dgrad(dx2, wd, rt.weight_t(unit, 5, wd))
+    dgu, hh = F_.swiglu_bwd_h(dhh, gu)
+    del dhh, gu
+    F_.linear_wgrad(dx2, hh, s[5][0], None, s[5][1])
+    del hh
+    F_.linear_wgrad(dgu, h2, s[4][0], None, s[4][1])
+    del h2
+    dh2 = F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, 4, wgu))
+    del dgu
+    shared = rt.grad_reducer()
+    red = shared if shared is not None else F_.GradReducer()
+    dx1 = F_.norm_bwd(dh2, x1, w_post, None, rstd2, dx2, s[3][0], None, s[3][1], True, red=red)
+    del dh2, x1, rstd2, dx2
+    F_.linear_wgrad(dx1, o, s[2][0], None, s[2][1])
+    do = F_.linear_dgrad(dx1, wo, rt.weight_t(unit, 2, wo))
+    # ---- attention half
+    window = 0 if ctx.bounds is not None else cfg.sliding_window or 0
+    if full:
+        _, h1, _, rstd1 = F_.norm_fwd(x, None, w_in, None, cfg.norm_eps, True)
+        qkv = F_.linear_fwd(h1, wqkv)
+        if model.cp is not None:      # the re-gather: one more all-gather per layer, in layer order on every rank
+            aux = _cp_rope_gather(model, qkv, Hq, Hkv, D)
+        else:
+            cos, sin = model.rope(x.device, T)
+            F_.rope_(qkv, cos, sin, T, Hq + Hkv, D, False)
+    else:
+        h1 = F_.norm_apply(x, w_in, None, None, rstd1, True)
+    dqkv = torch.empty_like(qkv)
+    if model.cp is not None:
+        _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed)
+    else:
+        cos, sin = model.rope(x.device, T)
+        F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
+                    dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
+                    1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds)
+        F_.rope_(dqkv, cos, sin, T, Hq + Hkv, D, True)
+    ctx.bounds = None
+    del qkv, aux, o, do, lse
+    F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
+    del h1
+    dh1 = F_.linear_dgrad(dqkv, wqkv, rt.weight_t(unit, 1, wqkv))
+    del dqkv
+    dx = F_.norm_bwd(dh1, x, w_in, None, rstd1, dx1, s[0][0], None, s[0][1], True, red=red)
+    if shared is None:
+        red.flush()
+    rt.grads_ready(unit)
+    rt.release_backward(unit)
+    return dx
 
 
 class _HeadFn(torch.autograd.Function):
@@ -272,6 +381,9 @@ class MistralLM(nn.Module):
         self.drop_p = 0.0
         self._rope = {}
         self.cp = None          # parallel.context.ContextParallel.attach(): a layout, not a model property
+        # which of a layer's activations its forward keeps for the backward (set by the harness, like cp):
+        # "off" all twelve, "selective" without h1 / h2 / hh, "full" only x, o, lse (_layer_backward_recompute)
+        self.activation_recompute = "off"
         self.unit_embed = Unit("embed", [("model.embed_tokens.weight", self.model.embed_tokens.weight)], 0)
         self.unit_blocks = [Unit(f"layers.{i}", [(f"model.layers.{i}.{n}", p) for n, p in layer.param_list()], i + 1)
                             for i, layer in enumerate(self.model.layers)]

@@ -40,6 +40,16 @@ def norm_fwd(x, r, w, b, eps, rms, p=0.0, seed=None, site=0, y_out=None):
     return s, _into(y_out, y), mean, rstd
 
 
+def norm_apply(s, w, b, mean, rstd, rms, y_out=None):
+    """y of :func:`norm_fwd` rebuilt from the residual stream ``s`` (the ``s`` norm_fwd returned, or its ``x`` when
+    it had no ``r``) and the ``mean`` / ``rstd`` it returned, bit for bit: one streaming pass without the row
+    reduction (csrc/norm.hip norm_apply_kernel).  ``y_out``: write y into this view (on the GPU its rows may be
+    strided)."""
+    if _gpu(s):
+        return ext().norm_apply(s, w, b, mean, rstd, rms, y_out)
+    return _into(y_out, ref.norm_apply(s, w, b, mean, rstd, rms))
+
+
 def norm_fwd_mask(x, r, w, b, eps, rms, p, seed, site, y_out, B, T, Hq, p_attn, attn_site, mask_out=None,
                   part=None):
     """norm_fwd plus the attention-dropout mask of (B, T, Hq) at ``attn_site``, on the GPU in one
@@ -342,6 +352,15 @@ def swiglu_fwd(gu):
 
 def swiglu_bwd(dh, gu):
     return ext().swiglu_bwd(dh, gu) if _gpu(dh) else ref.swiglu_bwd(dh, gu)
+
+
+def swiglu_bwd_h(dh, gu):
+    """(dgu, h) = (swiglu_bwd(dh, gu), swiglu_fwd(gu)), both bit for bit, from one pass over ``gu`` and ``dh``
+    (csrc/elementwise.hip swiglu_bwd_h_kernel): the SwiGLU backward of a forward that did not keep h."""
+    if _gpu(dh):
+        dgu, h = ext().swiglu_bwd_h(dh, gu)
+        return dgu, h
+    return ref.swiglu_bwd_h(dh, gu)
 
 
 def rope_(qkv2d, cos, sin, T, heads, D, inverse=False):

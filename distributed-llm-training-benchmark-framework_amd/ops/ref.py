@@ -55,6 +55,17 @@ def norm_fwd(x, r, w, b, eps, rms, p, seed, site):
     return s, y.to(dt), mean, rstd.reshape(-1)
 
 
+def norm_apply(s, w, b, mean, rstd, rms):
+    """y of :func:`norm_fwd` rebuilt from the stored residual stream ``s`` and the statistics it returned."""
+    x32 = _f(s)
+    rstd = rstd.reshape(x32.shape[:-1] + (1,))
+    if rms:
+        y = x32 * rstd * _f(w)
+    else:
+        y = (x32 - mean.reshape(x32.shape[:-1] + (1,))) * rstd * _f(w) + _f(b)
+    return y.to(s.dtype)
+
+
 def _write_slot(slot, val, accumulate):
     if slot is None:
         return
@@ -126,6 +137,11 @@ def swiglu_bwd(dh, gu):
     dg = d * u * s * (1 + g * (1 - s))
     du = d * g * s
     return torch.cat([dg, du], -1).to(gu.dtype)
+
+
+def swiglu_bwd_h(dh, gu):
+    """(dgu, h): :func:`swiglu_bwd` and the forward's h = :func:`swiglu_fwd` (gu), which the forward did not keep."""
+    return swiglu_bwd(dh, gu), swiglu_fwd(gu)
 
 
 def rope_tables(T, D, theta, device=None):

@@ -23,7 +23,8 @@ parameter *updates* of two runs compares their reduced gradients.  Rank 0 writes
 the two files.  ``--context-parallel N`` (with ``--cp-layout``) splits every row over groups of N consecutive
 ranks (dltb/parallel/context.py): the ranks of a group read the same rows, and the run must train the model the
 world-1 run trains.  Its Mistral-shape cases (``CP_CASES``: every strategy, a sliding window, packed documents)
-are not part of the default ``--cases``.  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
+are not part of the default ``--cases``.  ``--activation-recompute`` sets the Mistral-shape cases' saved set; a run
+with it must train the model the ``off`` run trains.  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
 DeepSpeed ZeRO-2/3 wrap) -- at any world size the trained model must be the one the global batch
 defines.
 """
@@ -107,6 +108,8 @@ def run_case(name, spec, world, rank, device, a):
     if cp > 1:
         from dltb.parallel.context import ContextParallel
         ContextParallel(cp, a.cp_layout, mcfg.sliding_window).attach(model)
+    if a.activation_recompute != "off":
+        model.activation_recompute = a.activation_recompute
     init = {n: p.detach().float().cpu().clone() for n, p in model.named_parameters()}
     fc = None
     if spec["strategy"] == "fsdp":
@@ -168,6 +171,8 @@ def main():
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--context-parallel", type=int, default=1, help="ranks per context-parallel group")
     ap.add_argument("--cp-layout", default="auto", choices=["auto", "contiguous", "zigzag"])
+    ap.add_argument("--activation-recompute", default="off", choices=["off", "selective", "full"],
+                    help="what the Mistral-shape cases keep for the backward (models/mistral.py)")
     a = ap.parse_args()
     from dltb.utils.dist import cleanup_distributed, setup_distributed
     world = int(os.environ.get("WORLD_SIZE", "1"))
