@@ -82,6 +82,11 @@ void dltb_embed_bwd_tok(const void* dx, const int64_t* sorted_ids, const int64_t
 // xent.hip
 void dltb_xent_fwd_bwd(void* logits, const int64_t* targets, float* loss, int N, int V,
                        int64_t ignore_index, hipStream_t st);
+// the two halves for a head that runs in row chunks: loss + log-sum-exp (logits only read), then dlogits in place
+void dltb_xent_lse(const void* logits, const int64_t* targets, float* loss, float* lse, int N, int V,
+                   int64_t ignore_index, hipStream_t st);
+void dltb_xent_bwd_lse(void* logits, const int64_t* targets, const float* lse, int N, int V,
+                       int64_t ignore_index, hipStream_t st);
 
 // adamw.hip
 int dltb_adamw_chunk();

@@ -7,6 +7,9 @@
 //     z_r (in place) <- softmax(z_r) - onehot(t_r)           (unscaled dlogits; 0 for ignored)
 // The 1/count mean-reduction and the incoming grad_output are applied by the caller as a device
 // scalar folded into the head GEMMs, so no host sync is needed anywhere.
+//
+// A head that processes its rows in chunks splits the two halves (xent_lse_kernel: loss and log-sum-exp, the
+// logits only read; xent_bwd_lse_kernel: dlogits from the recomputed logits and the kept log-sum-exp).
 #include "common.h"
 
 namespace {
@@ -90,6 +93,115 @@ __global__ __launch_bounds__(512) void xent_kernel(bf16_t* __restrict__ logits,
   }
 }
 
+// Block merge of the per-thread online-softmax pairs (m_t, sum exp(z - m_t)) into the row's (M, S): wave
+// butterfly, then the 8 waves through LDS in a fixed order.  xent_kernel's merge statement for statement (that
+// kernel keeps its own text, so its code object does not change): xent_lse_kernel's loss rows carry its bits.
+DLTB_DEV void xent_merge(float mt, float st, float* red, float* red2, float& M, float& S) {
+  float m = mt, sm = st;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float mo = __shfl_xor(m, off);
+    const float so = __shfl_xor(sm, off);
+    const float mn = fmaxf(m, mo);
+    sm = (m == -INFINITY ? 0.f : sm * __expf(m - mn)) + (mo == -INFINITY ? 0.f : so * __expf(mo - mn));
+    m = mn;
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[wid] = m;
+    red2[wid] = sm;
+  }
+  __syncthreads();
+  M = -INFINITY;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) M = fmaxf(M, red[w]);
+  S = 0.f;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) S += red[w] == -INFINITY ? 0.f : red2[w] * __expf(red[w] - M);
+}
+
+// The read-only half of xent_kernel, for a head that processes its rows in chunks and keeps no logits
+// (models/mistral.py, head_chunk): the same per-thread (max, sum) pass in the same order and the same block
+// merge, so loss[r] carries xent_kernel's bits, plus lse[r] = M + log S for xent_bwd_lse_kernel.  Nothing is
+// written back, so the row is held as its 16-bit words (VPT x 4 registers) and unpacked in both passes.
+template <int VPT>
+__global__ __launch_bounds__(512) void xent_lse_kernel(const bf16_t* __restrict__ logits,
+                                                      const int64_t* __restrict__ targets,
+                                                      float* __restrict__ loss, float* __restrict__ lse,
+                                                      int V, int64_t ignore_index) {
+  __shared__ float red[8], red2[8];
+  __shared__ float s_tlogit;
+  const int row = blockIdx.x;
+  const bf16_t* z = logits + (long)row * V;
+  const int64_t t = targets[row];
+  const bool valid = (t != ignore_index) && t >= 0 && t < V;
+  if (threadIdx.x == 0) s_tlogit = valid ? bf2f(z[t]) : 0.f;
+  const int nvec = V >> 3;
+  uint4 raw[VPT];
+  float mt = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) {
+    const int i = j * 512 + threadIdx.x;
+    if (i < nvec) {
+      raw[j] = ld16<uint4>(z + i * 8);
+      float f[8];
+      unpack8(raw[j], f);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) mt = fmaxf(mt, f[k]);
+    }
+  }
+  float st = 0.f;
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) {
+    const int i = j * 512 + threadIdx.x;
+    if (i < nvec) {
+      float f[8];
+      unpack8(raw[j], f);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) st += __expf(f[k] - mt);
+    }
+  }
+  float M, S;
+  xent_merge(mt, st, red, red2, M, S);
+  if (threadIdx.x == 0) {
+    loss[row] = valid ? (M + __logf(S) - s_tlogit) : 0.f;
+    lse[row] = M + __logf(S);
+  }
+}
+
+// dlogits of a chunk from its recomputed logits and the forward's lse, in place:
+//   z[r][c] <- exp(z[r][c] - lse[r]) - (c == t_r)          (0 for ignored rows and out-of-range targets)
+// No reduction, so the grid runs over the chunk's 16-byte vectors, not its rows (3 rows of V = 131072 are 192
+// workgroups): a workgroup takes 256 consecutive vectors, finds its first (row, column) by one wave-uniform
+// division and each thread its own by a 32-bit one; lse and the target are loaded per vector (cache hits).
+__global__ __launch_bounds__(256) void xent_bwd_lse_kernel(bf16_t* __restrict__ logits,
+                                                          const int64_t* __restrict__ targets,
+                                                          const float* __restrict__ lse, int N, int V,
+                                                          int64_t ignore_index) {
+  const uint32_t nvec = (uint32_t)V >> 3;
+  const long base = (long)blockIdx.x * 256;
+  const long row0 = base / nvec;
+  const uint32_t c = (uint32_t)(base - row0 * nvec) + threadIdx.x;      // < nvec + 256
+  const uint32_t q = c / nvec;
+  const long row = row0 + q;
+  if (row >= N) return;
+  const int col = (int)(c - q * nvec) * 8;
+  bf16_t* p = logits + row * V + col;
+  const int64_t t = targets[row];
+  const bool valid = (t != ignore_index) && t >= 0 && t < V;
+  float f[8];
+  if (valid) {
+    const float l = lse[row];
+    unpack8(ld16<uint4>(p), f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = __expf(f[k] - l) - (col + k == t ? 1.f : 0.f);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = 0.f;
+  }
+  *reinterpret_cast<uint4*>(p) = pack8(f);
+}
+
 // mean over non-ignored rows in one 1024-thread workgroup (fixed summation order):
 //   out[0] = sum(loss) / max(count, 1),  out[1] = max(count, 1)
 __global__ __launch_bounds__(1024) void xent_mean_kernel(const float* __restrict__ loss,
@@ -130,4 +242,26 @@ void dltb_xent_fwd_bwd(void* logits, const int64_t* targets, float* loss, int N,
   else if (vpt <= 16) DLTB_XE(16);
   else DLTB_XE(32);
 #undef DLTB_XE
+}
+
+void dltb_xent_lse(const void* logits, const int64_t* targets, float* loss, float* lse, int N, int V,
+                   int64_t ignore_index, hipStream_t st) {
+  const int vpt = cdiv(V / 8, 512);
+#define DLTB_XL(K)                                                                              \
+  hipLaunchKernelGGL(xent_lse_kernel<K>, dim3(N), dim3(512), 0, st, (const bf16_t*)logits, targets, \
+                     loss, lse, V, ignore_index)
+  if (vpt <= 1) DLTB_XL(1);
+  else if (vpt <= 2) DLTB_XL(2);
+  else if (vpt <= 4) DLTB_XL(4);
+  else if (vpt <= 8) DLTB_XL(8);
+  else if (vpt <= 16) DLTB_XL(16);
+  else DLTB_XL(32);
+#undef DLTB_XL
+}
+
+void dltb_xent_bwd_lse(void* logits, const int64_t* targets, const float* lse, int N, int V,
+                       int64_t ignore_index, hipStream_t st) {
+  const long blocks = ((long)N * (V / 8) + 255) / 256;
+  hipLaunchKernelGGL(xent_bwd_lse_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (bf16_t*)logits, targets,
+                     lse, N, V, ignore_index);
 }

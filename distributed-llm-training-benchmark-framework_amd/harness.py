@@ -14,7 +14,7 @@ Differences that make the numbers honest (recorded in the extended sidecar):
 * per-step losses stay on the device and are read once at the end (the reference syncs every step).
 Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device, --bucket-mb, --dropout, --seed,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
---doc-len, --context-parallel, --cp-layout, --activation-recompute.
+--doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk.
 """
 import argparse
 import json
@@ -79,6 +79,10 @@ def build_parser():
                         "kernels); full keeps only the layer input and the attention output (-88 %%) and re-runs "
                         "the qkv, o and gate|up projections in the backward (about a quarter more GEMM work per "
                         "step); attention itself is never re-run")
+    p.add_argument("--head-chunk", type=int, default=None, metavar="N",
+                   help="causal tiers: the LM head processes its rows (per_device_batch * seq_len / context_parallel) "
+                        "in chunks of N, a positive multiple of 16, and keeps their log-sum-exp instead of the "
+                        "[rows, vocab] logits; its backward re-runs the head product per chunk.  Default: off")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -187,6 +191,17 @@ def check_activation_recompute(mode, mcfg, tier):
                          "its activations in layer-strided buffers that its window-wide weight-gradient queue reads")
 
 
+def check_head_chunk(n, mcfg, tier):
+    """ValueError when ``--head-chunk`` is set for a tier without the chunked head, or to a value it cannot take."""
+    if n is None:
+        return
+    if not mcfg.causal:
+        raise ValueError(f"--head-chunk needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} ties its head to "
+                         "the token embedding and has no chunked head")
+    if n <= 0 or n % 16:
+        raise ValueError(f"--head-chunk must be a positive multiple of 16, got {n}")
+
+
 def train(args):
     world, rank, local_rank = resolve_ranks(args.world_size, args.rank, args.local_rank)
     args.world_size, args.rank, args.local_rank = world, rank, local_rank
@@ -247,12 +262,24 @@ def train(args):
         cp_layout = check_context_parallel(cp_n, getattr(args, "cp_layout", "auto"), world, mcfg, args.seq_len)
         recompute = getattr(args, "activation_recompute", None) or "off"
         check_activation_recompute(recompute, mcfg, args.tier)
+        head_chunk = getattr(args, "head_chunk", None)
+        check_head_chunk(head_chunk, mcfg, args.tier)
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
             model.activation_recompute = recompute
             if is_main:
                 print(f"Activation recompute: {recompute}", flush=True)
+        head_rows = args.per_device_batch * (args.seq_len // cp_n)      # the rows the head sees per micro-step
+        n_head_chunks = 1
+        if head_chunk is not None:
+            from .models.mistral import head_chunks
+            model.head_chunk = head_chunk
+            n_head_chunks = head_chunks(head_rows, head_chunk)
+            if is_main:
+                print(f"Head chunk: {head_chunk} rows, {n_head_chunks} chunk(s) of the {head_rows} rows per micro-step"
+                      + ("" if n_head_chunks > 1 else " (one chunk holds them all: the unchunked head runs)"),
+                      flush=True)
         cp = None
         if cp_n > 1:
             cp = _context.ContextParallel(cp_n, cp_layout, mcfg.sliding_window, world, rank)
@@ -408,6 +435,7 @@ def train(args):
                                         if cp_n > 1 else ""),
             "context_parallel": cp_n, "cp_layout": cp_layout if cp_n > 1 else None,
             "activation_recompute": recompute,
+            "head_chunk": head_chunk, "head_chunks": n_head_chunks,
             "cp_ranges": (cp.describe(args.seq_len)["cp_ranges"] if cp is not None else None),
             "tokens_per_micro_step": tokens_step,
             "timing": "barrier + device sync around the timed region; max over ranks (reference: rank-0 host "
@@ -489,6 +517,10 @@ def main(argv=None):
             parser.error(str(e))
     try:
         check_activation_recompute(args.activation_recompute, get_model_config(args.tier, args.seq_len), args.tier)
+    except ValueError as e:
+        parser.error(str(e))
+    try:
+        check_head_chunk(args.head_chunk, get_model_config(args.tier, args.seq_len), args.tier)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

@@ -320,9 +320,84 @@ def _layer_backward_recompute(ctx, dx2):
     return dx
 
 
+def _check_head_chunk(n):
+    if n is None:
+        return None
+    if isinstance(n, bool) or not isinstance(n, int) or n <= 0:
+        raise ValueError(f"head_chunk must be None or a positive integer (rows per chunk), got {n!r}")
+    return n
+
+
+def head_chunks(rows, n):
+    """How many chunks the head runs for ``rows`` rows under ``head_chunk = n``: 1 when off or when one chunk
+    would hold every row (then today's unchunked path runs: there is nothing to save)."""
+    return 1 if n is None or n >= rows else -(-rows // n)
+
+
+def _head_forward_chunked(ctx, x, model, targets, n):
+    """:meth:`_HeadFn.forward` under ``model.head_chunk = n < rows``: the logits exist one [n, V] chunk at a time
+    (each chunk's block returns to the allocator before the next product asks for it) and only their loss and
+    log-sum-exp rows are kept.  The loss rows are the unchunked path's wherever the chunk product's rows are."""
+    rt, unit = model.rt, model.unit_head
+    w_norm, w_head = rt.acquire(unit)
+    _, h, _, rstd = F_.norm_fwd(x, None, w_norm, None, model.cfg.norm_eps, True)
+    tg = targets.reshape(-1)
+    R = h.shape[0]
+    loss_rows = torch.empty(R, dtype=torch.float32, device=h.device)
+    lse = torch.empty(R, dtype=torch.float32, device=h.device)
+    for r0 in range(0, R, n):
+        r1 = min(r0 + n, R)
+        logits = F_.linear_fwd(h[r0:r1], w_head)
+        F_.xent_lse(logits, tg[r0:r1], -1, loss_rows[r0:r1], lse[r0:r1])
+        del logits
+    lc = F_.xent_mean(loss_rows, tg, -1)          # (mean, count) over all rows, as unchunked
+    loss, count = lc[0], lc[1:2]
+    rt.release_forward(unit)
+    ctx.model, ctx.no_loss, ctx.chunk = model, False, n
+    ctx.saved = (x, h, rstd, lse, tg, count)
+    out_logits = h.new_empty(0)
+    ctx.mark_non_differentiable(out_logits)
+    return out_logits, loss
+
+
+def _head_backward_chunked(ctx, dloss):
+    """The backward of :func:`_head_forward_chunked`: per chunk the forward product again (same call, same inputs,
+    so the forward's logits bit for bit), dlogits in place from the kept log-sum-exp, then the two gradient
+    products -- the weight gradient accumulating into its slot from the second chunk on.  The scale g and the
+    scaled hs are the whole batch's, and the norm backward runs once on the assembled dh."""
+    model, n = ctx.model, ctx.chunk
+    rt, unit = model.rt, model.unit_head
+    (x, h, rstd, lse, tg, count) = ctx.saved
+    ctx.saved = None
+    w_norm, w_head = rt.acquire_backward(unit)
+    dwh, acc_h = rt.grad_slot(unit, 1)
+    hs, g = F_.scale_by(h, dloss, count)                      # g = dloss / count (device)
+    wt = rt.weight_t(unit, 1, w_head)
+    R = h.shape[0]
+    dh = torch.empty_like(h)
+    for r0 in range(0, R, n):
+        r1 = min(r0 + n, R)
+        dl = F_.linear_fwd(h[r0:r1], w_head)
+        F_.xent_bwd_lse_(dl, tg[r0:r1], lse[r0:r1], -1)
+        F_.linear_wgrad(dl, hs[r0:r1], dwh, None, acc_h if r0 == 0 else True)
+        dh[r0:r1].copy_(F_.head_dgrad(dl, w_head, wt, g))
+        del dl
+    del h, hs, lse
+    gw, acc = rt.grad_slot(unit, 0)
+    dx = F_.norm_bwd(dh, x, w_norm, None, rstd, None, gw, None, acc, True)
+    rt.grads_ready(unit)
+    rt.release_backward(unit)
+    return dx
+
+
 class _HeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, model, targets, return_logits):
+        n = _check_head_chunk(model.head_chunk)
+        ctx.chunk = None
+        # the caller wants the logits (no targets, return_logits), or one chunk holds them all: the unchunked path
+        if n is not None and n < x.shape[0] and targets is not None and not return_logits:
+            return _head_forward_chunked(ctx, x, model, targets, n)
         rt, unit = model.rt, model.unit_head
         w_norm, w_head = rt.acquire(unit)
         _, h, _, rstd = F_.norm_fwd(x, None, w_norm, None, model.cfg.norm_eps, True)
@@ -348,6 +423,8 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, dlogits_unused, dloss):
         if ctx.no_loss:
             return None, None, None, None
+        if ctx.chunk is not None:
+            return _head_backward_chunked(ctx, dloss), None, None, None
         model = ctx.model
         rt, unit = model.rt, model.unit_head
         (x, h, rstd, dl, count) = ctx.saved
@@ -384,6 +461,9 @@ class MistralLM(nn.Module):
         # which of a layer's activations its forward keeps for the backward (set by the harness, like cp):
         # "off" all twelve, "selective" without h1 / h2 / hh, "full" only x, o, lse (_layer_backward_recompute)
         self.activation_recompute = "off"
+        # rows per chunk of the LM head (set by the harness too): None materialises the [rows, V] logits and keeps
+        # them as dlogits for the backward; N keeps their log-sum-exp rows and re-runs the product per chunk
+        self.head_chunk = None
         self.unit_embed = Unit("embed", [("model.embed_tokens.weight", self.model.embed_tokens.weight)], 0)
         self.unit_blocks = [Unit(f"layers.{i}", [(f"model.layers.{i}.{n}", p) for n, p in layer.param_list()], i + 1)
                             for i, layer in enumerate(self.model.layers)]

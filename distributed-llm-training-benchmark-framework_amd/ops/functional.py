@@ -390,6 +390,25 @@ def xent_fwd_bwd_(logits2d, targets1d, ignore_index=-1):
     return ref.xent_fwd_bwd_(logits2d, targets1d, ignore_index)
 
 
+def xent_lse(logits2d, targets1d, ignore_index=-1, loss_out=None, lse_out=None):
+    """(loss rows, log-sum-exp rows) in fp32 of a logits chunk that is only read (the chunked head's forward);
+    the loss rows are :func:`xent_fwd_bwd_`'s bit for bit.  ``loss_out`` / ``lse_out``: contiguous f32 [N]
+    slices of the caller's whole-batch rows."""
+    if _gpu(logits2d):
+        loss, lse = ext().xent_lse(logits2d, targets1d, ignore_index, loss_out, lse_out)
+        return loss, lse
+    loss, lse = ref.xent_lse(logits2d, targets1d, ignore_index)
+    return _into(loss_out, loss), _into(lse_out, lse)
+
+
+def xent_bwd_lse_(logits2d, targets1d, lse, ignore_index=-1):
+    """logits <- exp(logits - lse) - onehot(targets) in place (0 for ignored rows): the chunked head's
+    backward on its recomputed logits."""
+    if _gpu(logits2d):
+        return ext().xent_bwd_lse_(logits2d, targets1d, lse, ignore_index)
+    return ref.xent_bwd_lse_(logits2d, targets1d, lse, ignore_index)
+
+
 def xent_mean(loss_rows, targets1d, ignore_index=-1):
     """f32[2] = (mean loss over non-ignored rows, max(count, 1)), computed on the device (one
     launch on MI355X instead of compare / sum / clamp / cast / div)."""

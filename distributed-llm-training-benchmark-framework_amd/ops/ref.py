@@ -202,6 +202,29 @@ def xent_fwd_bwd_(logits, targets, ignore_index):
     return loss
 
 
+def xent_lse(logits, targets, ignore_index):
+    """(per-row loss, per-row log-sum-exp) in fp32; the logits are only read.  The loss is
+    :func:`xent_fwd_bwd_`'s, the same expressions on the same values."""
+    z = _f(logits)
+    valid = targets != ignore_index
+    lse = torch.logsumexp(z, -1)
+    tl = z.gather(-1, targets.clamp(min=0)[:, None])[:, 0]
+    return torch.where(valid, lse - tl, torch.zeros_like(lse)), lse
+
+
+def xent_bwd_lse_(logits, targets, lse, ignore_index):
+    """Overwrites logits with unscaled ``exp(z - lse) - onehot`` (0 for ignored rows) from the kept
+    log-sum-exp: :func:`xent_fwd_bwd_`'s gradient without its reduction.  Returns logits."""
+    z = _f(logits)
+    valid = targets != ignore_index
+    t = targets.clamp(min=0)
+    pr = torch.exp(z - lse.to(torch.float32)[:, None])
+    pr.scatter_add_(-1, t[:, None], -torch.ones_like(pr[:, :1]))
+    pr = torch.where(valid[:, None], pr, torch.zeros_like(pr))
+    logits.copy_(pr.to(logits.dtype))
+    return logits
+
+
 # ------------------------------------------------------------------------------ attention
 def check_window(window, causal):
     """Sliding window ``W >= 1``: query i sees key j iff ``i - W < j <= i`` (W keys including its own, the

@@ -24,7 +24,8 @@ the two files.  ``--context-parallel N`` (with ``--cp-layout``) splits every row
 ranks (dltb/parallel/context.py): the ranks of a group read the same rows, and the run must train the model the
 world-1 run trains.  Its Mistral-shape cases (``CP_CASES``: every strategy, a sliding window, packed documents)
 are not part of the default ``--cases``.  ``--activation-recompute`` sets the Mistral-shape cases' saved set; a run
-with it must train the model the ``off`` run trains.  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
+with it must train the model the ``off`` run trains; so must one with ``--head-chunk N`` (the Mistral-shape cases' LM
+head in chunks of N rows).  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
 DeepSpeed ZeRO-2/3 wrap) -- at any world size the trained model must be the one the global batch
 defines.
 """
@@ -110,6 +111,8 @@ def run_case(name, spec, world, rank, device, a):
         ContextParallel(cp, a.cp_layout, mcfg.sliding_window).attach(model)
     if a.activation_recompute != "off":
         model.activation_recompute = a.activation_recompute
+    if a.head_chunk is not None and hasattr(model, "head_chunk"):      # the Mistral-shape cases only
+        model.head_chunk = a.head_chunk
     init = {n: p.detach().float().cpu().clone() for n, p in model.named_parameters()}
     fc = None
     if spec["strategy"] == "fsdp":
@@ -173,6 +176,8 @@ def main():
     ap.add_argument("--cp-layout", default="auto", choices=["auto", "contiguous", "zigzag"])
     ap.add_argument("--activation-recompute", default="off", choices=["off", "selective", "full"],
                     help="what the Mistral-shape cases keep for the backward (models/mistral.py)")
+    ap.add_argument("--head-chunk", type=int, default=None,
+                    help="rows per chunk of the Mistral-shape cases' LM head (models/mistral.py); default: unchunked")
     a = ap.parse_args()
     from dltb.utils.dist import cleanup_distributed, setup_distributed
     world = int(os.environ.get("WORLD_SIZE", "1"))
