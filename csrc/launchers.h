@@ -164,6 +164,27 @@ void dltb_colpart(const DltbColPartSeg* segs, int nseg, int P, uint32_t thr16, f
                   const int64_t* seed, hipStream_t st);
 void dltb_colreduce_multi(const DltbColRedSeg* segs, int nseg, hipStream_t st);
 
+// ---- moe.hip: top-k routing with a fixed capacity of C slots per expert (rows = E * C); N token rows of width d
+// (a multiple of 8), 1 <= K <= 4, K <= E <= 64.  expert / slot [N][K], src / src_k [rows], counts [E] are int32,
+// gate [N][K], logits / dlogits [N][E] fp32.  slot = -1: dropped; src = -1: empty slot.
+void dltb_moe_route(const void* h, const void* wr, int* expert, float* gate, float* logits, int N, int d, int E,
+                    int K, hipStream_t st);
+// scratch: int32 [2][ceil(N K / 64)][E]
+void dltb_moe_assign(const int* expert, int* scratch, int* slot, int* src, int* src_k, int* counts, int N, int K,
+                     int E, int C, hipStream_t st);
+void dltb_moe_dispatch(const void* h, const int* src, void* xe, int rows, int N, int d, hipStream_t st);
+void dltb_moe_combine(const void* ye, const int* slot, const float* gate, void* m, int N, int d, int K, int rows,
+                      hipStream_t st);
+void dltb_moe_combine_bwd(const void* dm, const void* ye, const int* slot, const int* src, const int* expert,
+                          const float* gate, void* dye, float* dgate, float* dlogits, int N, int d, int E, int K,
+                          int rows, hipStream_t st);
+void dltb_moe_dispatch_bwd(const void* dxe, const int* slot, const float* dlogits, const void* wr, void* dh, int N,
+                           int d, int E, int K, int rows, hipStream_t st);
+int dltb_moe_wgrad_partials(int N, int E, int d);
+// part: fp32 [P][E][d], P = dltb_moe_wgrad_partials(N, E, d)
+void dltb_moe_router_wgrad(const float* dlogits, const void* h, float* part, void* dwr, int accumulate, int N, int d,
+                           int E, int P, hipStream_t st);
+
 // ---- gemm.hip: C[M,N] = A B (+bias) (+C); NT: A [M][K], B [N][K]; TN: A [K][M], B [K][N]
 bool dltb_gemm_supported(int M, int N, int K, bool tn, int cfg);
 int dltb_gemm(const void* a, const void* b, void* c, const void* bias, float* part, long lda, long ldb,

@@ -14,7 +14,8 @@ Differences that make the numbers honest (recorded in the extended sidecar):
 * per-step losses stay on the device and are read once at the end (the reference syncs every step).
 Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device, --bucket-mb, --dropout, --seed,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
---doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk.
+--doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk, --moe-experts, --moe-top-k,
+--moe-capacity-factor.
 """
 import argparse
 import json
@@ -83,6 +84,14 @@ def build_parser():
                    help="causal tiers: the LM head processes its rows (per_device_batch * seq_len / context_parallel) "
                         "in chunks of N, a positive multiple of 16, and keeps their log-sum-exp instead of the "
                         "[rows, vocab] logits; its backward re-runs the head product per chunk.  Default: off")
+    p.add_argument("--moe-experts", type=int, default=None, metavar="E",
+                   help="causal tiers: replace every layer's FFN by E (2..64) SwiGLU experts behind a top-k router with "
+                        "a fixed capacity per expert (assignments past it are dropped); default: the dense FFN")
+    p.add_argument("--moe-top-k", type=int, default=None, metavar="K",
+                   help="experts per token with --moe-experts: 1, 2 or 4 (default 2)")
+    p.add_argument("--moe-capacity-factor", type=float, default=None, metavar="F",
+                   help="with --moe-experts: slots per expert = min(ceil(F * rows * K / E), rows) rounded up to a "
+                        "multiple of 16, rows = per_device_batch * seq_len / context_parallel (default 1.25)")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -202,6 +211,26 @@ def check_head_chunk(n, mcfg, tier):
         raise ValueError(f"--head-chunk must be a positive multiple of 16, got {n}")
 
 
+def check_moe(experts, top_k, factor, recompute, mcfg, tier):
+    """ValueError when the ``--moe-*`` flags are set for a tier without the routed FFN or together with
+    ``--activation-recompute``; sets them on ``mcfg`` (whose ``validate`` refuses out-of-range values)."""
+    if experts is None:
+        if top_k is not None or factor is not None:
+            raise ValueError("--moe-top-k / --moe-capacity-factor are only used together with --moe-experts")
+        return
+    if not mcfg.causal:
+        raise ValueError(f"--moe-experts needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the "
+                         "reference's dense GELU MLP")
+    if recompute != "off":
+        raise ValueError(f"--activation-recompute {recompute} is not supported together with --moe-experts")
+    mcfg.n_experts = experts
+    if top_k is not None:
+        mcfg.moe_top_k = top_k
+    if factor is not None:
+        mcfg.moe_capacity_factor = factor
+    mcfg.validate()
+
+
 def train(args):
     world, rank, local_rank = resolve_ranks(args.world_size, args.rank, args.local_rank)
     args.world_size, args.rank, args.local_rank = world, rank, local_rank
@@ -264,6 +293,8 @@ def train(args):
         check_activation_recompute(recompute, mcfg, args.tier)
         head_chunk = getattr(args, "head_chunk", None)
         check_head_chunk(head_chunk, mcfg, args.tier)
+        check_moe(getattr(args, "moe_experts", None), getattr(args, "moe_top_k", None),
+                  getattr(args, "moe_capacity_factor", None), recompute, mcfg, args.tier)
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -280,6 +311,11 @@ def train(args):
                 print(f"Head chunk: {head_chunk} rows, {n_head_chunks} chunk(s) of the {head_rows} rows per micro-step"
                       + ("" if n_head_chunks > 1 else " (one chunk holds them all: the unchunked head runs)"),
                       flush=True)
+        if mcfg.n_experts and is_main:
+            from .ops.ref import moe_capacity
+            print(f"Mixture of experts: {mcfg.n_experts} experts, top-{mcfg.moe_top_k}, capacity "
+                  f"{moe_capacity(head_rows, mcfg.n_experts, mcfg.moe_top_k, mcfg.moe_capacity_factor)} slots per "
+                  f"expert for the {head_rows} rows per micro-step (factor {mcfg.moe_capacity_factor})", flush=True)
         cp = None
         if cp_n > 1:
             cp = _context.ContextParallel(cp_n, cp_layout, mcfg.sliding_window, world, rank)
@@ -436,6 +472,8 @@ def train(args):
             "context_parallel": cp_n, "cp_layout": cp_layout if cp_n > 1 else None,
             "activation_recompute": recompute,
             "head_chunk": head_chunk, "head_chunks": n_head_chunks,
+            # the last micro-step's assignments per layer and expert (before drops), read once, here
+            "moe": model.moe_stats(head_rows) if mcfg.n_experts else None,
             "cp_ranges": (cp.describe(args.seq_len)["cp_ranges"] if cp is not None else None),
             "tokens_per_micro_step": tokens_step,
             "timing": "barrier + device sync around the timed region; max over ranks (reference: rank-0 host "
@@ -521,6 +559,11 @@ def main(argv=None):
         parser.error(str(e))
     try:
         check_head_chunk(args.head_chunk, get_model_config(args.tier, args.seq_len), args.tier)
+    except ValueError as e:
+        parser.error(str(e))
+    try:
+        check_moe(args.moe_experts, args.moe_top_k, args.moe_capacity_factor, args.activation_recompute,
+                  get_model_config(args.tier, args.seq_len), args.tier)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

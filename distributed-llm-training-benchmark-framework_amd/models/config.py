@@ -39,6 +39,12 @@ class ModelConfig:
     # packed sequences: a token equal to doc_eos_id ends a document (and belongs to it); attention does not cross
     # document boundaries.  None = every row is one document.  Causal only; composes with sliding_window.
     doc_eos_id: Optional[int] = None
+    # mixture of experts (mistral arch): n_experts SwiGLU FFNs per layer behind a top-k router with a fixed capacity of
+    # min(ceil(moe_capacity_factor * rows * moe_top_k / n_experts), rows) slots per expert, rounded up to a multiple
+    # of 16 (assignments past it are dropped).  None = the dense FFN.
+    n_experts: Optional[int] = None
+    moe_top_k: int = 2
+    moe_capacity_factor: float = 1.25
 
     def __post_init__(self):
         self.validate()
@@ -57,6 +63,23 @@ class ModelConfig:
                 raise ValueError(f"doc_eos_id must be an integer in [0, vocab_size) or None, got {e!r}")
             if not self.causal:
                 raise ValueError("doc_eos_id (document-masked attention) needs causal=True")
+        k, cf = self.moe_top_k, self.moe_capacity_factor
+        if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4):
+            raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
+        if isinstance(cf, bool) or not isinstance(cf, (int, float)) or not 0.0 < cf < float("inf"):
+            raise ValueError(f"moe_capacity_factor must be a positive finite number, got {cf!r}")
+        ne = self.n_experts
+        if ne is not None:
+            if isinstance(ne, bool) or not isinstance(ne, int) or not 2 <= ne <= 64:
+                raise ValueError(f"n_experts must be an integer in [2, 64] or None, got {ne!r}")
+            if self.arch != "mistral":
+                raise ValueError(f"n_experts (mixture-of-experts FFN) needs the mistral arch, got arch {self.arch!r}")
+            if k > ne:
+                raise ValueError(f"moe_top_k = {k} exceeds n_experts = {ne}")
+            if self.n_embd % 64:
+                raise ValueError(f"n_experts needs n_embd to be a multiple of 64, got {self.n_embd}")
+        elif self.arch != "mistral" and (k != 2 or cf != 1.25):
+            raise ValueError(f"moe_top_k / moe_capacity_factor need the mistral arch, got arch {self.arch!r}")
 
     @property
     def head_dim(self) -> int:
@@ -82,7 +105,10 @@ class ModelConfig:
             return V * d + self.block_size * d + L * per_block + 2 * d
         hd = self.head_dim
         kvd = self.kv_heads * hd
-        per_block = d + (d * d + 2 * kvd * d) + d * d + d + 3 * d * self.ffn_dim
+        ffn = 3 * d * self.ffn_dim
+        if self.n_experts:       # every expert's FFN plus the router
+            ffn = self.n_experts * ffn + self.n_experts * d
+        per_block = d + (d * d + 2 * kvd * d) + d * d + d + ffn
         head = 0 if self.tie_embeddings else V * d
         return V * d + L * per_block + d + head
 
@@ -91,13 +117,17 @@ class ModelConfig:
         W < T a row sees (W (T - W) + W^2 / 2) / T keys on average instead of T / 2).
         ``visible_pairs_per_row``: the measured number of visible (query, key) pairs of a row of ``seq_len``
         tokens (a document mask depends on the data: ``SyntheticDataset.visible_pairs_per_row``); it replaces
-        the T^2 / 2 (or window) count.  Without it the result is exactly the formula above."""
+        the T^2 / 2 (or window) count.  Without it the result is exactly the formula above.  With ``n_experts`` the
+        FFN term counts ``moe_top_k`` experts and the router product per token."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d
         else:
             kvd = self.kv_heads * self.head_dim
-            n_mat = L * (2 * d * d + 2 * kvd * d + 3 * d * self.ffn_dim) + self.vocab_size * d
+            ffn = 3 * d * self.ffn_dim
+            if self.n_experts:   # nominal: the moe_top_k experts a token is routed to (drops not subtracted) + router
+                ffn = self.moe_top_k * ffn + self.n_experts * d
+            n_mat = L * (2 * d * d + 2 * kvd * d + ffn) + self.vocab_size * d
         attn = 12 * L * seq_len * d * (0.5 if self.causal else 1.0)
         w = self.sliding_window
         if self.causal and w is not None and w < seq_len:

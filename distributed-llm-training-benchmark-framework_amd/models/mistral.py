@@ -16,6 +16,9 @@ Parameter names follow the common fused-projection layout:
 ``model.layers.{i}.self_attn.{qkv_proj,o_proj}.weight``, ``model.layers.{i}.mlp.{gate_up_proj,down_proj}.weight``,
 ``model.norm.weight``, ``lm_head.weight``.  RMSNorm / RoPE / SwiGLU / causal-GQA attention / xent
 run as dltb HIP kernels on the GPU.
+
+With ``cfg.n_experts`` the FFN is a top-k mixture of experts with a fixed capacity per expert (``_moe_fwd`` /
+``_moe_bwd``, csrc/moe.hip): ``mlp`` then holds ``router.weight`` and ``experts.{e}.{gate_up_proj,down_proj}.weight``.
 """
 import math
 
@@ -48,6 +51,15 @@ class _MLP(nn.Module):
         self.down_proj = nn.Linear(f, d, bias=False)
 
 
+class _MoE(nn.Module):
+    """``cfg.n_experts`` SwiGLU FFNs behind a top-k router (the layer's ``mlp`` when ``n_experts`` is set)."""
+
+    def __init__(self, d, f, n_experts):
+        super().__init__()
+        self.router = nn.Linear(d, n_experts, bias=False)
+        self.experts = nn.ModuleList([_MLP(d, f) for _ in range(n_experts)])
+
+
 class MistralLayer(nn.Module):
     def __init__(self, cfg: ModelConfig):
         super().__init__()
@@ -55,15 +67,21 @@ class MistralLayer(nn.Module):
         self.input_layernorm = _RMSNorm(d)
         self.self_attn = _Attn(d, cfg.kv_heads * cfg.head_dim)
         self.post_attention_layernorm = _RMSNorm(d)
-        self.mlp = _MLP(d, cfg.ffn_dim)
+        self.mlp = _MoE(d, cfg.ffn_dim, cfg.n_experts) if cfg.n_experts else _MLP(d, cfg.ffn_dim)
 
     def param_list(self):
-        return [("input_layernorm.weight", self.input_layernorm.weight),
+        head = [("input_layernorm.weight", self.input_layernorm.weight),
                 ("self_attn.qkv_proj.weight", self.self_attn.qkv_proj.weight),
                 ("self_attn.o_proj.weight", self.self_attn.o_proj.weight),
-                ("post_attention_layernorm.weight", self.post_attention_layernorm.weight),
-                ("mlp.gate_up_proj.weight", self.mlp.gate_up_proj.weight),
-                ("mlp.down_proj.weight", self.mlp.down_proj.weight)]
+                ("post_attention_layernorm.weight", self.post_attention_layernorm.weight)]
+        if isinstance(self.mlp, _MoE):      # the router, then every expert's pair: parameters 4, 5 + 2e, 6 + 2e
+            moe = [("mlp.router.weight", self.mlp.router.weight)]
+            for e, ex in enumerate(self.mlp.experts):
+                moe += [(f"mlp.experts.{e}.gate_up_proj.weight", ex.gate_up_proj.weight),
+                        (f"mlp.experts.{e}.down_proj.weight", ex.down_proj.weight)]
+            return head + moe
+        return head + [("mlp.gate_up_proj.weight", self.mlp.gate_up_proj.weight),
+                       ("mlp.down_proj.weight", self.mlp.down_proj.weight)]
 
 
 class _EmbedFn(torch.autograd.Function):
@@ -148,8 +166,13 @@ class _LayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, model, i):
         rt, unit = model.rt, model.unit_blocks[i]
-        (w_in, wqkv, wo, w_post, wgu, wd) = rt.acquire(unit)
         cfg = model.cfg
+        ctx.recompute = _check_recompute(model.activation_recompute)
+        if cfg.n_experts and ctx.recompute != "off":
+            raise ValueError("--activation-recompute is not supported together with --moe-experts "
+                             f"(activation_recompute = {ctx.recompute!r}, n_experts = {cfg.n_experts})")
+        ws = rt.acquire(unit)
+        (w_in, wqkv, wo, w_post) = ws[:4]
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
         _, h1, _, rstd1 = F_.norm_fwd(x, None, w_in, None, cfg.norm_eps, True)
@@ -167,14 +190,19 @@ class _LayerFn(torch.autograd.Function):
                                       1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds)
         a = F_.linear_fwd(o, wo)
         x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
-        gu = F_.linear_fwd(h2, wgu)
-        hh = F_.swiglu_fwd(gu)
-        m = F_.linear_fwd(hh, wd)
+        ctx.moe = None
+        if cfg.n_experts:       # top-k routed experts instead of the dense FFN; gu / hh are per expert, in ctx.moe
+            m, ctx.moe = _moe_fwd(model, i, h2, ws[4:])
+            gu = hh = None
+        else:
+            wgu, wd = ws[4:]
+            gu = F_.linear_fwd(h2, wgu)
+            hh = F_.swiglu_fwd(gu)
+            m = F_.linear_fwd(hh, wd)
         x2 = F_.dropout(x1, m, 0.0, rt.seed, 0)
         rt.release_forward(unit)
         ctx.model, ctx.i = model, i
         ctx.saved = (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh)
-        ctx.recompute = _check_recompute(model.activation_recompute)
         if ctx.recompute == "selective":      # the backward rebuilds h1, h2 (norm_apply) and hh (swiglu_bwd_h)
             ctx.saved = (x, None, rstd1, qkv, o, lse, aux, x1, None, rstd2, gu, None)
         elif ctx.recompute == "full":         # ... and everything else but the attention output
@@ -190,17 +218,23 @@ class _LayerFn(torch.autograd.Function):
         rt, unit = model.rt, model.unit_blocks[i]
         (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh) = ctx.saved
         ctx.saved = None
-        (w_in, wqkv, wo, w_post, wgu, wd) = rt.acquire_backward(unit)
+        ws = rt.acquire_backward(unit)
+        (w_in, wqkv, wo, w_post) = ws[:4]
         cfg = model.cfg
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
         dx2 = dx2.contiguous()
-        s = [rt.grad_slot(unit, j) for j in range(6)]
-        F_.linear_wgrad(dx2, hh, s[5][0], None, s[5][1])
-        dhh = F_.linear_dgrad(dx2, wd, rt.weight_t(unit, 5, wd))
-        dgu = F_.swiglu_bwd(dhh, gu)
-        F_.linear_wgrad(dgu, h2, s[4][0], None, s[4][1])
-        dh2 = F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, 4, wgu))
+        s = [rt.grad_slot(unit, j) for j in range(len(ws))]
+        if ctx.moe is not None:
+            dh2 = _moe_bwd(model, unit, dx2, h2, ws, s, ctx.moe)
+            ctx.moe = None
+        else:
+            wgu, wd = ws[4:]
+            F_.linear_wgrad(dx2, hh, s[5][0], None, s[5][1])
+            dhh = F_.linear_dgrad(dx2, wd, rt.weight_t(unit, 5, wd))
+            dgu = F_.swiglu_bwd(dhh, gu)
+            F_.linear_wgrad(dgu, h2, s[4][0], None, s[4][1])
+            dh2 = F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, 4, wgu))
         shared = rt.grad_reducer()
         red = shared if shared is not None else F_.GradReducer()
         dx1 = F_.norm_bwd(dh2, x1, w_post, None, rstd2, dx2, s[3][0], None, s[3][1], True, red=red)
@@ -226,6 +260,55 @@ class _LayerFn(torch.autograd.Function):
         rt.grads_ready(unit)
         rt.release_backward(unit)
         return dx, None, None
+
+
+def _moe_fwd(model, i, h2, ws):
+    """The routed FFN of layer ``i`` on the rows ``h2`` [N, d]; ``ws``: the router, then (gate_up, down) per expert.
+    Route (top-k, softmax gates), assign slots (fixed capacity C per expert, row-major order, overflow dropped),
+    gather the rows into ``xe`` [E C, d], run each expert's SwiGLU FFN on its [C, d] slab with the dense path's
+    GEMM calls, and combine.  Every shape is static.  Returns (m, what the backward needs)."""
+    cfg = model.cfg
+    E, K = cfg.n_experts, cfg.moe_top_k
+    C = ref.moe_capacity(h2.shape[0], E, K, cfg.moe_capacity_factor)
+    expert, gate, _ = F_.moe_route(h2, ws[0], K)
+    slot, src, _, _ = F_.moe_assign(expert, E, C, model.moe_counts(h2.device)[i])
+    xe = F_.moe_dispatch(h2, src)
+    ye = torch.empty_like(xe)
+    gus, hhs = [], []
+    for e in range(E):
+        rows = slice(e * C, (e + 1) * C)
+        gu = F_.linear_fwd(xe[rows], ws[1 + 2 * e])
+        hh = F_.swiglu_fwd(gu)
+        ye[rows].copy_(F_.linear_fwd(hh, ws[2 + 2 * e]))
+        gus.append(gu)
+        hhs.append(hh)
+    m = F_.moe_combine(ye, slot, gate)
+    return m, (expert, gate, slot, src, xe, ye, gus, hhs, C)
+
+
+def _moe_bwd(model, unit, dm, h2, ws, s, saved):
+    """The backward of :func:`_moe_fwd`, in gather form throughout: returns dh2 and writes the router's and every
+    expert's weight gradient into its slot (``ws`` / ``s``: the unit's parameters and gradient slots; the router is
+    parameter 4, expert e's pair 5 + 2e and 6 + 2e).  An expert without tokens sees zero slabs, so its gradients
+    are exact zeros."""
+    rt = model.rt
+    (expert, gate, slot, src, xe, ye, gus, hhs, C) = saved
+    E = model.cfg.n_experts
+    dye, _, dlogits = F_.moe_combine_bwd(dm, ye, slot, src, expert, gate, E)
+    del ye
+    dxe = torch.empty_like(xe)
+    for e in range(E):
+        rows = slice(e * C, (e + 1) * C)
+        ju, jd = 5 + 2 * e, 6 + 2 * e
+        wgu, wd = ws[ju], ws[jd]
+        F_.linear_wgrad(dye[rows], hhs[e], s[jd][0], None, s[jd][1])
+        dhh = F_.linear_dgrad(dye[rows], wd, rt.weight_t(unit, jd, wd))
+        dgu = F_.swiglu_bwd(dhh, gus[e])
+        gus[e] = hhs[e] = None
+        F_.linear_wgrad(dgu, xe[rows], s[ju][0], None, s[ju][1])
+        dxe[rows].copy_(F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, ju, wgu)))
+    F_.moe_router_wgrad(dlogits, h2, s[4][0], s[4][1])
+    return F_.moe_dispatch_bwd(dxe, slot, dlogits, ws[4])
 
 
 RECOMPUTE_MODES = ("off", "selective", "full")
@@ -464,6 +547,7 @@ class MistralLM(nn.Module):
         # rows per chunk of the LM head (set by the harness too): None materialises the [rows, V] logits and keeps
         # them as dlogits for the backward; N keeps their log-sum-exp rows and re-runs the product per chunk
         self.head_chunk = None
+        self._moe_counts = None     # int32 [n_layer, n_experts]: the last micro-step's assignments per expert
         self.unit_embed = Unit("embed", [("model.embed_tokens.weight", self.model.embed_tokens.weight)], 0)
         self.unit_blocks = [Unit(f"layers.{i}", [(f"model.layers.{i}.{n}", p) for n, p in layer.param_list()], i + 1)
                             for i, layer in enumerate(self.model.layers)]
@@ -481,6 +565,30 @@ class MistralLM(nn.Module):
 
     def num_params(self):
         return sum(p.numel() for p in self.parameters())
+
+    def moe_counts(self, device):
+        """int32 [n_layer, n_experts], row i written by layer i's slot assignment every micro-step (before drops)."""
+        if self._moe_counts is None or self._moe_counts.device.type != torch.device(device).type:
+            self._moe_counts = torch.zeros(self.cfg.n_layer, self.cfg.n_experts, dtype=torch.int32, device=device)
+        return self._moe_counts
+
+    def moe_stats(self, rows):
+        """The ``moe`` block of the harness's extended record for micro-steps of ``rows`` local token rows: reads the
+        last micro-step's counts (one device-to-host copy; call it after the timed steps).  The figures are the
+        calling rank's alone: under world > 1 or context parallelism they cover its local rows."""
+        cfg = self.cfg
+        E, K = cfg.n_experts, cfg.moe_top_k
+        C = ref.moe_capacity(rows, E, K, cfg.moe_capacity_factor)
+        out = {"experts": E, "top_k": K, "capacity_factor": cfg.moe_capacity_factor, "capacity": C,
+               "counts": None, "drop_fraction": None,
+               "scope": "this rank's local token rows of the last micro-step (not summed over ranks): counts per "
+                        "layer and expert before drops; drop_fraction pooled over the layers"}
+        if self._moe_counts is not None:
+            counts = self._moe_counts.cpu()
+            out["counts"] = counts.tolist()
+            total = int(counts.sum())
+            out["drop_fraction"] = float((counts - C).clamp(min=0).sum()) / total if total else 0.0
+        return out
 
     def forward(self, idx, targets=None, return_logits=False):
         B, T = idx.shape

@@ -70,6 +70,32 @@ def _rope(x, cos, sin):
     return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], -1)
 
 
+def _moe_ffn(mlp, h, cfg):
+    """Top-k routed experts with a fixed capacity on the rows ``h`` [N, d], differentiated by autograd alone: the
+    K largest router logits per row (ties to the lower expert), softmax gates over them, slots in row-major
+    (token, choice) order with overflow dropped (the integer bookkeeping is ``ops.ref.moe_assign``: nothing to
+    differentiate), each expert's SwiGLU FFN on its slab, gate-weighted sum."""
+    from ..ops import ref
+    N = h.shape[0]
+    E, K = cfg.n_experts, cfg.moe_top_k
+    C = ref.moe_capacity(N, E, K, cfg.moe_capacity_factor)
+    vals, idx = torch.sort(mlp.router(h), dim=-1, descending=True, stable=True)
+    gate = torch.softmax(vals[:, :K], -1)
+    slot, src, _, _ = ref.moe_assign(idx[:, :K].to(torch.int32), E, C)
+    zero = torch.zeros((), dtype=h.dtype, device=h.device)
+    xe = torch.where((src >= 0)[:, None], h[src.clamp(min=0).long()], zero)
+    ys = []
+    for e, ex in enumerate(mlp.experts):
+        g, u = ex.gate_up_proj(xe[e * C:(e + 1) * C]).chunk(2, -1)
+        ys.append(ex.down_proj(F.silu(g) * u))
+    ye = torch.cat(ys, 0)
+    out = torch.zeros_like(h)
+    for k in range(K):
+        s = slot[:, k]
+        out = out + torch.where((s >= 0)[:, None], gate[:, k:k + 1] * ye[s.clamp(min=0).long()], zero)
+    return out
+
+
 class OracleMistral(nn.Module):
     """Stock-op Mistral-shape decoder with the same parameter names as dltb.models.mistral."""
 
@@ -89,8 +115,17 @@ class OracleMistral(nn.Module):
             layer.self_attn.o_proj = nn.Linear(d, d, bias=False)
             layer.post_attention_layernorm = _RMSNorm(d, cfg.norm_eps)
             layer.mlp = nn.Module()
-            layer.mlp.gate_up_proj = nn.Linear(d, 2 * cfg.ffn_dim, bias=False)
-            layer.mlp.down_proj = nn.Linear(cfg.ffn_dim, d, bias=False)
+            if cfg.n_experts:       # mixture of experts: a router and n_experts FFNs (autograd only, _moe_ffn)
+                layer.mlp.router = nn.Linear(d, cfg.n_experts, bias=False)
+                layer.mlp.experts = nn.ModuleList()
+                for _e in range(cfg.n_experts):
+                    ex = nn.Module()
+                    ex.gate_up_proj = nn.Linear(d, 2 * cfg.ffn_dim, bias=False)
+                    ex.down_proj = nn.Linear(cfg.ffn_dim, d, bias=False)
+                    layer.mlp.experts.append(ex)
+            else:
+                layer.mlp.gate_up_proj = nn.Linear(d, 2 * cfg.ffn_dim, bias=False)
+                layer.mlp.down_proj = nn.Linear(cfg.ffn_dim, d, bias=False)
             self.model.layers.append(layer)
         self.model.norm = _RMSNorm(d, cfg.norm_eps)
         self.lm_head = nn.Linear(d, cfg.vocab_size, bias=False)
@@ -127,6 +162,9 @@ class OracleMistral(nn.Module):
             else:
                 o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
             x = x + layer.self_attn.o_proj(o.transpose(1, 2).reshape(B, T, H * hd))
+            if cfg.n_experts:
+                x = x + _moe_ffn(layer.mlp, layer.post_attention_layernorm(x).reshape(B * T, -1), cfg).view_as(x)
+                continue
             gu = layer.mlp.gate_up_proj(layer.post_attention_layernorm(x))
             g, u = gu.chunk(2, -1)
             x = x + layer.mlp.down_proj(F.silu(g) * u)

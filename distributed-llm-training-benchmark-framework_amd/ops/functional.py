@@ -363,6 +363,57 @@ def swiglu_bwd_h(dh, gu):
     return ref.swiglu_bwd_h(dh, gu)
 
 
+# ------------------------------------------------------------------------------ mixture of experts
+# Top-k routing with a fixed expert capacity (csrc/moe.hip; semantics and layouts: ref.py).  Every shape is static
+# and no kernel uses atomics, so a captured micro-step replays bit for bit.
+def moe_route(h, wr, K):
+    """(expert int32 [N, K], gate f32 [N, K], logits f32 [N, E]) of the router ``wr`` [E, d] on the rows ``h``."""
+    if _gpu(h):
+        expert, gate, logits = ext().moe_route(h, wr, K)
+        return expert, gate, logits
+    return ref.moe_route(h, wr, K)
+
+
+def moe_assign(expert, E, C, counts_out=None):
+    """(slot [N, K], src [E C], src_k [E C], counts [E]), all int32.  ``counts_out``: a contiguous int32 [E] tensor
+    that receives the counts (the model's per-layer row, read by the harness after the run)."""
+    if _gpu(expert):
+        slot, src, src_k, counts = ext().moe_assign(expert, E, C, counts_out)
+        return slot, src, src_k, counts
+    slot, src, src_k, counts = ref.moe_assign(expert, E, C)
+    return slot, src, src_k, _into(counts_out, counts)
+
+
+def moe_dispatch(h, src):
+    return ext().moe_dispatch(h, src) if _gpu(h) else ref.moe_dispatch(h, src)
+
+
+def moe_combine(ye, slot, gate):
+    return ext().moe_combine(ye, slot, gate) if _gpu(ye) else ref.moe_combine(ye, slot, gate)
+
+
+def moe_combine_bwd(dm, ye, slot, src, expert, gate, E):
+    """(dye, dgate f32 [N, K], dlogits f32 [N, E]) from one pass over ``dm`` and ``ye``."""
+    if _gpu(dm):
+        dye, dgate, dlogits = ext().moe_combine_bwd(dm, ye, slot, src, expert, gate, E)
+        return dye, dgate, dlogits
+    return ref.moe_combine_bwd(dm, ye, slot, src, expert, gate, E)
+
+
+def moe_dispatch_bwd(dxe, slot, dlogits, wr):
+    if _gpu(dxe):
+        return ext().moe_dispatch_bwd(dxe, slot, dlogits, wr)
+    return ref.moe_dispatch_bwd(dxe, slot, dlogits, wr)
+
+
+def moe_router_wgrad(dlogits, h, dwr, accumulate):
+    """dWr (+)= dlogits^T h into the router's gradient slot (fixed-order two-stage column reduction)."""
+    if _gpu(h):
+        ext().moe_router_wgrad(dlogits, h, dwr, bool(accumulate))
+    else:
+        ref.moe_router_wgrad(dlogits, h, dwr, accumulate)
+
+
 def rope_(qkv2d, cos, sin, T, heads, D, inverse=False):
     if _gpu(qkv2d):
         ext().rope_(qkv2d, cos, sin, T, heads, D, inverse)

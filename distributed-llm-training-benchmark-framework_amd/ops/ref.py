@@ -382,6 +382,105 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, s
     dv.copy_(dvh.transpose(1, 2).reshape(B * T, Hkv * D).to(dv.dtype))
 
 
+# ------------------------------------------------------------------------------ mixture of experts
+# Top-k routing with a fixed capacity (csrc/moe.hip).  N token rows, E experts, K choices per token, C slots per
+# expert.  Index tensors are int32: expert / slot [N, K], src / src_k [E * C], counts [E]; slot -1 = dropped
+# assignment, src -1 = empty slot.  fp64 inputs stay fp64 (precision tests).
+MOE_MAX_EXPERTS = 64
+MOE_TOP_K = (1, 2, 4)
+
+
+def moe_capacity(N, E, K, factor):
+    """Slots per expert: min(ceil(factor N K / E), N), rounded up to a multiple of 16 (the GEMMs' row granularity)."""
+    c = min(int(math.ceil(factor * N * K / E)), N)
+    return -(-c // 16) * 16
+
+
+def moe_route(h, wr, K):
+    """(expert, gate, logits): logits = h Wr^T in fp32; the K largest per row, ordered by descending logit, ties by
+    ascending expert index; gates = softmax over the K chosen logits."""
+    logits = _f(h) @ _f(wr).t()
+    vals, idx = torch.sort(logits, dim=-1, descending=True, stable=True)
+    sel = vals[:, :K]
+    ex = torch.exp(sel - sel[:, :1])
+    return idx[:, :K].to(torch.int32).contiguous(), ex / ex.sum(-1, keepdim=True), logits
+
+
+def moe_assign(expert, E, C):
+    """(slot, src, src_k, counts).  Assignment (n, k) to expert e gets position p = the number of assignments to e
+    among the earlier (n', k') in row-major order; its slot is e C + p, or -1 (dropped) when p >= C.  src / src_k:
+    the token row and choice held by each slot.  counts: assignments per expert before dropping."""
+    N, K = expert.shape
+    flat = expert.reshape(-1).long()
+    onehot = F.one_hot(flat, E)
+    pos = (onehot.cumsum(0) - onehot).gather(1, flat[:, None]).squeeze(1)
+    keep = pos < C
+    slot = torch.where(keep, flat * C + pos, torch.full_like(pos, -1))
+    src = torch.full((E * C,), -1, dtype=torch.int32, device=expert.device)
+    src_k = torch.full((E * C,), -1, dtype=torch.int32, device=expert.device)
+    i = torch.arange(N * K, device=expert.device)[keep]
+    src[slot[keep]] = (i // K).to(torch.int32)
+    src_k[slot[keep]] = (i % K).to(torch.int32)
+    return slot.to(torch.int32).view(N, K), src, src_k, onehot.sum(0).to(torch.int32)
+
+
+def _moe_rows(t, index):
+    """t[index] with zero rows where index < 0."""
+    ok = (index >= 0)[:, None]
+    return torch.where(ok, t[index.clamp(min=0).long()], torch.zeros((), dtype=t.dtype, device=t.device))
+
+
+def moe_dispatch(h, src):
+    """xe[s] = h[src[s]]; empty slots are exactly zero."""
+    return _moe_rows(h, src)
+
+
+def moe_combine(ye, slot, gate):
+    """m[n] = sum_k gate[n, k] ye[slot[n, k]] over the kept k, in k order in fp32, rounded once."""
+    y = _f(ye)
+    acc = torch.zeros(slot.shape[0], y.shape[1], dtype=y.dtype, device=y.device)
+    for k in range(slot.shape[1]):
+        acc = acc + gate[:, k:k + 1].to(y.dtype) * _moe_rows(y, slot[:, k])
+    return acc.to(ye.dtype)
+
+
+def moe_combine_bwd(dm, ye, slot, src, expert, gate, E):
+    """(dye, dgate, dlogits): dye[s] = gate(s) dm[src[s]] (zero rows for empty slots), dgate[n, k] =
+    <dm[n], ye[slot[n, k]]> (0 when dropped), and the softmax backward dlogit_k = g_k (dgate_k - sum_j g_j dgate_j)
+    scattered into a dense [N, E] row (0 for the experts not chosen)."""
+    d32, y = _f(dm), _f(ye)
+    g = gate.to(d32.dtype)
+    N, K = slot.shape
+    dgate = torch.zeros(N, K, dtype=d32.dtype, device=d32.device)
+    dye = torch.zeros_like(y)
+    for k in range(K):
+        s = slot[:, k].long()
+        ok = s >= 0
+        dgate[:, k] = (d32 * _moe_rows(y, slot[:, k])).sum(-1)      # zero rows where dropped
+        dye[s[ok]] = (g[:, k:k + 1] * d32)[ok]
+    dl = g * (dgate - (g * dgate).sum(-1, keepdim=True))
+    dlogits = torch.zeros(N, E, dtype=d32.dtype, device=d32.device).scatter_(1, expert.long(), dl)
+    return dye.to(ye.dtype), dgate, dlogits
+
+
+def moe_dispatch_bwd(dxe, slot, dlogits, wr):
+    """dh[n] = sum_k dxe[slot[n, k]] + sum_e dlogits[n, e] Wr[e], in fp32, rounded once."""
+    x = _f(dxe)
+    acc = torch.zeros(slot.shape[0], x.shape[1], dtype=x.dtype, device=x.device)
+    for k in range(slot.shape[1]):
+        acc = acc + _moe_rows(x, slot[:, k])
+    return (acc + dlogits.to(x.dtype) @ _f(wr).to(x.dtype)).to(dxe.dtype)
+
+
+def moe_router_wgrad(dlogits, h, dwr, accumulate):
+    """dWr (+)= dlogits^T h into the router's gradient slot."""
+    h32 = _f(h)
+    v = dlogits.to(h32.dtype).t() @ h32
+    if accumulate:
+        v = v + _f(dwr)
+    dwr.copy_(v)
+
+
 # ------------------------------------------------------------------------------ optimizer
 def adamw_flat(master, exp_avg, exp_avg_sq, grad, lr, beta1, beta2, eps, wd, step, gscale=None):
     g = _f(grad)

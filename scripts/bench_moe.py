@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""What the top-k mixture-of-experts FFN costs on one MI355X (writes profiles/moe_layer.txt).
+
+    python scripts/bench_moe.py [--out profiles/moe_layer.txt] [--rows 4096,16384] [--factors 1.0,1.25,2.0] [--reps 9]
+
+Times the FFN part of one MoE layer at the M7B shape (d 4096, f 14336, E 8, K 2), forward plus backward: route,
+assign, dispatch, the E experts, combine and their backward (``models/mistral.py::_moe_fwd`` / ``_moe_bwd``).  The
+baseline is the dense SwiGLU FFN on the same rows with hidden size K f: equal nominal FLOPs.  Both run on the same
+device in one process, interleaved rep by rep after a warm-up, and the medians are reported.  The seven routing
+kernels are also timed one by one on the same tensors, and so are the 2 E slab copies the layer makes (each expert's
+output and data gradient is copied into its rows of the slot buffer); kernels plus copies over the layer's time is the
+share the routing takes beside the GEMMs and SwiGLU kernels.  The drop fraction is that of the random-init router on
+normal rows.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b), out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "moe_layer.txt"))
+    ap.add_argument("--rows", default="4096,16384")
+    ap.add_argument("--factors", default="1.0,1.25,2.0")
+    ap.add_argument("--experts", type=int, default=8)
+    ap.add_argument("--top-k", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=9)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_moe.py measures on the GPU; none found")
+    import dltb  # noqa: F401
+    from dltb.models import get_model_config, mistral
+    from dltb.ops import functional as F_
+    from dltb.ops import ref
+    from dltb.parallel import ParamRuntime
+
+    dev, dt = "cuda", torch.bfloat16
+    E, K = a.experts, a.top_k
+    base = get_model_config("M7B", 4096)
+    d, f = base.n_embd, base.ffn_dim
+    lines = [f"# scripts/bench_moe.py on {torch.cuda.get_device_name(0)}, torch {torch.__version__}",
+             f"# one layer's FFN part, forward + backward, bf16, d {d}, f {f}, E {E}, K {K}; dense baseline: hidden {K * f}",
+             f"# medians of {a.reps} interleaved reps after 3 warm-up reps; ms",
+             "rows factor capacity drop_fraction moe_ms dense_ms ratio routing_kernels_ms slab_copies_ms routing_share"]
+
+    def layer(n_experts, ffn, factor):
+        cfg = get_model_config("M7B", 4096)
+        cfg.n_layer, cfg.vocab_size, cfg.ffn_hidden = 1, 256, ffn
+        if n_experts:
+            cfg.n_experts, cfg.moe_top_k, cfg.moe_capacity_factor = n_experts, K, factor
+        cfg.validate()
+        torch.manual_seed(0)
+        with torch.device(dev):
+            m = mistral.MistralLM(cfg).to(dt)
+        m.rt = ParamRuntime()
+        return m
+
+    dense = layer(None, K * f, 1.0)
+    du = dense.unit_blocks[0]
+    dws = dense.rt.acquire(du)
+    ds = [(torch.empty_like(w), False) for w in dws]
+    for rows in [int(r) for r in a.rows.split(",")]:
+        h = torch.randn(rows, d, device=dev).to(dt)
+        dm = torch.randn(rows, d, device=dev).to(dt)
+
+        def dense_step():
+            gu = F_.linear_fwd(h, dws[4])
+            hh = F_.swiglu_fwd(gu)
+            F_.linear_fwd(hh, dws[5])
+            F_.linear_wgrad(dm, hh, ds[5][0], None, False)
+            dgu = F_.swiglu_bwd(F_.linear_dgrad(dm, dws[5]), gu)
+            F_.linear_wgrad(dgu, h, ds[4][0], None, False)
+            return F_.linear_dgrad(dgu, dws[4])
+
+        for factor in [float(x) for x in a.factors.split(",")]:
+            moe = layer(E, f, factor)
+            mu = moe.unit_blocks[0]
+            mws = moe.rt.acquire(mu)
+            ms = [(torch.empty_like(w), False) for w in mws]
+
+            def moe_step():
+                _, saved = mistral._moe_fwd(moe, 0, h, mws[4:])
+                return mistral._moe_bwd(moe, mu, dm, h, mws, ms, saved)
+
+            t_moe, t_dense = [], []
+            for rep in range(a.reps + 3):
+                tm, _ = _timed(moe_step)
+                td, _ = _timed(dense_step)
+                if rep >= 3:
+                    t_moe.append(tm)
+                    t_dense.append(td)
+            C = ref.moe_capacity(rows, E, K, factor)
+            counts = moe.moe_counts(dev)[0].cpu()
+            drop = float((counts - C).clamp(min=0).sum()) / float(counts.sum())
+            # the seven routing kernels alone, on the tensors of one forward
+            expert, gate, _ = F_.moe_route(h, mws[4], K)
+            slot, src, _, _ = F_.moe_assign(expert, E, C)
+            xe = F_.moe_dispatch(h, src)
+            _, _, dl = F_.moe_combine_bwd(dm, xe, slot, src, expert, gate, E)
+            dwr = torch.empty_like(mws[4])
+            kernels = [lambda: F_.moe_route(h, mws[4], K), lambda: F_.moe_assign(expert, E, C),
+                       lambda: F_.moe_dispatch(h, src), lambda: F_.moe_combine(xe, slot, gate),
+                       lambda: F_.moe_combine_bwd(dm, xe, slot, src, expert, gate, E),
+                       lambda: F_.moe_dispatch_bwd(xe, slot, dl, mws[4]),
+                       lambda: F_.moe_router_wgrad(dl, h, dwr, False)]
+            t_k = 0.0
+            for k in kernels:
+                for _ in range(3):
+                    k()
+                t_k += statistics.median(_timed(k)[0] for _ in range(a.reps))
+            slab, part = torch.empty_like(xe), torch.randn(C, d, device=dev).to(dt)
+
+            def copies():      # what _moe_fwd / _moe_bwd copy: E outputs into ye, E data gradients into dxe
+                for _ in range(2):
+                    for e in range(E):
+                        slab[e * C:(e + 1) * C].copy_(part)
+
+            for _ in range(3):
+                copies()
+            t_c = statistics.median(_timed(copies)[0] for _ in range(a.reps))
+            mm, md = statistics.median(t_moe), statistics.median(t_dense)
+            lines.append(f"{rows} {factor} {C} {drop:.4f} {mm:.3f} {md:.3f} {mm / md:.3f} {t_k:.3f} {t_c:.3f} "
+                         f"{(t_k + t_c) / mm:.3f}")
+            print(lines[-1], flush=True)
+            del moe, mws, ms
+            torch.cuda.empty_cache()
+    lines.append(f"# written {time.strftime('%Y-%m-%d')}; the step time of a whole model under --moe-experts is not measured")
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print(f"wrote {a.out}")
+
+
+if __name__ == "__main__":
+    main()

@@ -101,8 +101,13 @@ def run_case(name, spec, world, rank, device, a):
         mcfg.sliding_window = int(spec["window"])
     if spec.get("doc_len"):
         mcfg.doc_eos_id = mcfg.vocab_size - 1
-    if spec.get("window") or spec.get("doc_len"):
-        mcfg.validate()
+    if a.doc_len and mcfg.causal:      # --doc-len: every Mistral-shape case packs documents
+        spec = dict(spec, doc_len=a.doc_len)
+        mcfg.doc_eos_id = mcfg.vocab_size - 1
+    if a.moe_experts is not None and mcfg.arch == "mistral":      # the Mistral-shape cases only
+        mcfg.n_experts, mcfg.moe_top_k = a.moe_experts, a.moe_top_k
+        mcfg.moe_capacity_factor = a.moe_capacity_factor
+    mcfg.validate()
     with torch.device(device):
         model = build_model(mcfg)
     cp = a.context_parallel
@@ -178,6 +183,12 @@ def main():
                     help="what the Mistral-shape cases keep for the backward (models/mistral.py)")
     ap.add_argument("--head-chunk", type=int, default=None,
                     help="rows per chunk of the Mistral-shape cases' LM head (models/mistral.py); default: unchunked")
+    ap.add_argument("--doc-len", type=int, default=None,
+                    help="pack documents of this mean length into the rows of the Mistral-shape cases")
+    ap.add_argument("--moe-experts", type=int, default=None,
+                    help="experts per layer of the Mistral-shape cases (models/mistral.py); default: the dense FFN")
+    ap.add_argument("--moe-top-k", type=int, default=2)
+    ap.add_argument("--moe-capacity-factor", type=float, default=1.25)
     a = ap.parse_args()
     from dltb.utils.dist import cleanup_distributed, setup_distributed
     world = int(os.environ.get("WORLD_SIZE", "1"))
