@@ -184,6 +184,16 @@ int dltb_moe_wgrad_partials(int N, int E, int d);
 // part: fp32 [P][E][d], P = dltb_moe_wgrad_partials(N, E, d)
 void dltb_moe_router_wgrad(const float* dlogits, const void* h, float* part, void* dwr, int accumulate, int N, int d,
                            int E, int P, hipStream_t st);
+// the same for dense dlogits: 8 experts per block, so h is read ceil(E / 8) times (same part, same fold)
+void dltb_moe_router_wgrad_dense(const float* dlogits, const void* h, float* part, void* dwr, int accumulate, int N,
+                                 int d, int E, int P, hipStream_t st);
+// auxiliary router losses: lse [N], out (and out2 when not null) [2] = (balance, z); part: fp32
+// [dltb_moe_aux_partials(N)][65].  g [2]: the incoming gradients of (balance, z), on the device.
+int dltb_moe_aux_partials(int N);
+void dltb_moe_aux_fwd(const float* logits, const int* counts, float* lse, float* part, float* out, float* out2, int N,
+                      int E, int K, hipStream_t st);
+void dltb_moe_aux_bwd(float* dlogits, const float* logits, const float* lse, const int* counts, const float* g, int N,
+                      int E, int K, hipStream_t st);
 
 // ---- gemm.hip: C[M,N] = A B (+bias) (+C); NT: A [M][K], B [N][K]; TN: A [K][M], B [K][N]
 bool dltb_gemm_supported(int M, int N, int K, bool tn, int cfg);

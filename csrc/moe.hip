@@ -13,7 +13,10 @@
 //                     dlogits row (one pass over dm and ye; empty slots get zero rows)
 //   moe_dispatch_bwd  dh[n] = sum_k dxe[slot[n, k]] + sum_e dlogits[n, e] Wr[e], fp32, rounded once
 //   moe_router_wgrad  dWr = dlogits^T h: fp32 row-range partials per expert (only rows with a non-zero dlogit
-//                     are read), then colreduce_multi's fixed-order sum into the gradient slot
+//                     are read), then colreduce_multi's fixed-order sum into the gradient slot; a dense form
+//                     for a dlogits without zeros (8 experts per pass over h), same partials and fold
+//   moe_aux_fwd       load-balancing loss and router z-loss of the logits and the counts (fixed-order partials)
+//   moe_aux_bwd       their gradient added to the dense dlogits, softmax recomputed from the kept log-sum-exp
 // Rows are moved as 16-byte chunks, lane -> chunk, chunks strided by the wave; index arrays are trusted only
 // as far as a bound check (an index outside its range counts as dropped / empty).
 #include "common.h"
@@ -428,6 +431,167 @@ void dltb_moe_router_wgrad(const float* dlogits, const void* h, float* part, voi
                            int E, int P, hipStream_t st) {
   hipLaunchKernelGGL(moe_router_wgrad_kernel, dim3(cdiv(d, 512), P, E), dim3(256), 0, st, dlogits, (const bf16_t*)h,
                      part, N, d, E, P);
+  DltbColRedSeg seg{};
+  seg.part = part;
+  seg.out = (uint16_t*)dwr;
+  seg.P = P;
+  seg.k = E * d;
+  seg.accumulate = accumulate;
+  dltb_colreduce_multi(&seg, 1, st);
+}
+
+// ---------------------------------------------------------------- auxiliary router losses
+// balance = E sum_e f[e] P[e] (f[e] = counts[e] / (N K), a constant; P[e] = mean_n softmax(logits[n])[e]) and
+// z = mean_n lse[n]^2, lse = logsumexp(logits[n]).  Forward: per-block partials of sum_n p[n, e] and sum_n lse^2,
+// folded in block order by a second, one-block launch.  Backward: p = exp(logits - lse) again, added in place.
+namespace {
+
+constexpr int AUX_ROWS = 16;                 // rows per wave in the forward: 64 rows per block and per partial
+constexpr int AUX_PART = 65;                 // a partial: 64 column sums of p, then the sum of lse^2
+
+__global__ __launch_bounds__(256) void moe_aux_fwd_kernel(const float* __restrict__ logits, float* __restrict__ lse,
+                                                          float* __restrict__ part, int N, int E) {
+  __shared__ float red[4][AUX_PART];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  DLTB_DCHECK(E >= 1 && E <= 64);
+  const int n0 = (blockIdx.x * 4 + wv) * AUX_ROWS;
+  const int n1 = min(N, n0 + AUX_ROWS);      // wave-uniform; every wave reaches the barrier below
+  float psum = 0.f, zsum = 0.f;
+  for (int n = n0; n < n1; ++n) {
+    const float v = lane < E ? logits[(size_t)n * E + lane] : -INFINITY;
+    const float mx = wave_max(v);
+    const float ex = lane < E ? expf(v - mx) : 0.f;
+    const float s = wave_sum(ex);             // xor butterfly: the same bits in every lane
+    const float l = mx + logf(s);
+    if (lane == 0) lse[n] = l;
+    psum += ex / s;
+    zsum = fmaf(l, l, zsum);
+  }
+  red[wv][lane] = psum;
+  if (lane == 0) red[wv][64] = zsum;
+  __syncthreads();
+  if (threadIdx.x < AUX_PART) {
+    const int c = threadIdx.x;
+    part[(size_t)blockIdx.x * AUX_PART + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+  }
+}
+
+// one block: wave w folds the partials b = w, w + 4, ... in ascending order (lane = column), the waves are added in
+// wave order; the z column is strided over the 256 threads and summed by block_sum
+__global__ __launch_bounds__(256) void moe_aux_fin_kernel(const float* __restrict__ part, const int* __restrict__ counts,
+                                                          float* __restrict__ out, float* __restrict__ out2, int nb,
+                                                          int N, int E, int K) {
+  __shared__ float red[4][64];
+  __shared__ float redz[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float ps = 0.f, zs = 0.f;
+  for (int b = wv; b < nb; b += 4) ps += part[(size_t)b * AUX_PART + lane];
+  for (int b = threadIdx.x; b < nb; b += 256) zs += part[(size_t)b * AUX_PART + 64];
+  red[wv][lane] = ps;
+  const float z = block_sum(zs, redz);       // its barriers also order red
+  if (wv != 0) return;
+  const float invn = 1.f / (float)N;
+  const float P = ((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane])) * invn;
+  const float f = lane < E ? (float)counts[lane] / ((float)N * (float)K) : 0.f;
+  const float bal = (float)E * wave_sum(lane < E ? f * P : 0.f);
+  if (lane == 0) {
+    out[0] = bal;
+    out[1] = z * invn;
+    if (out2 != nullptr) {
+      out2[0] = bal;
+      out2[1] = z * invn;
+    }
+  }
+}
+
+// one wave per row, lane = expert: dlogits[n, e] += g_b (E / N) p (f[e] - sum_j f[j] p[j]) + g_z (2 / N) lse p
+__global__ __launch_bounds__(256) void moe_aux_bwd_kernel(float* __restrict__ dlogits, const float* __restrict__ logits,
+                                                          const float* __restrict__ lse, const int* __restrict__ counts,
+                                                          const float* __restrict__ g, int N, int E, int K) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;                                    // wave-uniform; the kernel has no block barrier
+  DLTB_DCHECK(E >= 1 && E <= 64);
+  const bool on = lane < E;
+  const size_t i = (size_t)n * E + (on ? lane : 0);
+  const float l = lse[n];
+  const float p = on ? expf(logits[i] - l) : 0.f;
+  const float f = on ? (float)counts[lane] / ((float)N * (float)K) : 0.f;
+  const float dot = wave_sum(f * p);
+  const float cb = g[0] * ((float)E / (float)N);         // the incoming gradients enter as one factor each: a power
+  const float cz = g[1] * (2.f / (float)N);              // of two on them scales the added term exactly
+  const float add = fmaf(cb, p * (f - dot), cz * (l * p));
+  if (on) dlogits[i] += add;
+}
+
+// The router weight gradient for dense dlogits (every entry non-zero once an auxiliary loss is on): a block takes the
+// rows [by rps, +rps) for 8 experts at once (64 fp32 accumulators per lane), so h is read ceil(E / 8) times, not E
+// times.  Same part[P][E][d] layout, row order and fold as moe_router_wgrad_kernel.
+__global__ __launch_bounds__(256) void moe_router_wgrad_dense_kernel(const float* __restrict__ dlogits,
+                                                                     const bf16_t* __restrict__ h,
+                                                                     float* __restrict__ part, int N, int d, int E,
+                                                                     int P) {
+  __shared__ __attribute__((aligned(16))) float red[4][512];
+  const int lane = threadIdx.x & 63;
+  const int phase = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int e0 = blockIdx.z * 8;
+  const int col = blockIdx.x * 512 + lane * 8;
+  const int rps = (N + P - 1) / P;
+  const int r0 = blockIdx.y * rps, r1 = min(N, r0 + rps);
+  float acc[8][8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[j][i] = 0.f;
+  if (col < d) {
+#pragma unroll 2
+    for (int r = r0 + phase; r < r1; r += 4) {            // ascending rows
+      float hv[8];
+      unpack8(ld16<uint4>(h + (size_t)r * d + col), hv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = e0 + j < E ? dlogits[(size_t)r * E + e0 + j] : 0.f;      // wave-uniform
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[j][i] = fmaf(v, hv[i], acc[j][i]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (e0 + j >= E) break;                               // block-uniform
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) red[phase][lane * 8 + i] = acc[j][i];
+    __syncthreads();
+    for (int c = threadIdx.x; c < 512; c += 256) {
+      const int gc = blockIdx.x * 512 + c;
+      if (gc < d)
+        part[((size_t)blockIdx.y * E + e0 + j) * d + gc] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+    }
+  }
+}
+
+}  // namespace
+
+int dltb_moe_aux_partials(int N) { return cdiv(N, 4 * AUX_ROWS); }
+
+void dltb_moe_aux_fwd(const float* logits, const int* counts, float* lse, float* part, float* out, float* out2, int N,
+                      int E, int K, hipStream_t st) {
+  const int nb = dltb_moe_aux_partials(N);
+  hipLaunchKernelGGL(moe_aux_fwd_kernel, dim3(nb), dim3(256), 0, st, logits, lse, part, N, E);
+  hipLaunchKernelGGL(moe_aux_fin_kernel, dim3(1), dim3(256), 0, st, (const float*)part, counts, out, out2, nb, N, E,
+                     K);
+}
+
+void dltb_moe_aux_bwd(float* dlogits, const float* logits, const float* lse, const int* counts, const float* g, int N,
+                      int E, int K, hipStream_t st) {
+  hipLaunchKernelGGL(moe_aux_bwd_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, dlogits, logits, lse, counts, g, N, E, K);
+}
+
+void dltb_moe_router_wgrad_dense(const float* dlogits, const void* h, float* part, void* dwr, int accumulate, int N,
+                                 int d, int E, int P, hipStream_t st) {
+  hipLaunchKernelGGL(moe_router_wgrad_dense_kernel, dim3(cdiv(d, 512), P, cdiv(E, 8)), dim3(256), 0, st, dlogits,
+                     (const bf16_t*)h, part, N, d, E, P);
   DltbColRedSeg seg{};
   seg.part = part;
   seg.out = (uint16_t*)dwr;

@@ -15,7 +15,7 @@ Differences that make the numbers honest (recorded in the extended sidecar):
 Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device, --bucket-mb, --dropout, --seed,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
 --doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk, --moe-experts, --moe-top-k,
---moe-capacity-factor.
+--moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef.
 """
 import argparse
 import json
@@ -92,6 +92,13 @@ def build_parser():
     p.add_argument("--moe-capacity-factor", type=float, default=None, metavar="F",
                    help="with --moe-experts: slots per expert = min(ceil(F * rows * K / E), rows) rounded up to a "
                         "multiple of 16, rows = per_device_batch * seq_len / context_parallel (default 1.25)")
+    p.add_argument("--moe-aux-loss-coef", type=float, default=None, metavar="A",
+                   help="with --moe-experts: add A times the load-balancing loss E * sum_e f_e * P_e of every layer to "
+                        "the loss (f_e: the fraction of the rank's assignments that chose expert e, P_e: its mean "
+                        "router probability); default 0: off")
+    p.add_argument("--moe-z-loss-coef", type=float, default=None, metavar="B",
+                   help="with --moe-experts: add B times the router z-loss mean(logsumexp(logits)^2) of every layer "
+                        "to the loss; default 0: off")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -211,12 +218,19 @@ def check_head_chunk(n, mcfg, tier):
         raise ValueError(f"--head-chunk must be a positive multiple of 16, got {n}")
 
 
-def check_moe(experts, top_k, factor, recompute, mcfg, tier):
+def check_moe(experts, top_k, factor, recompute, mcfg, tier, aux_coef=None, z_coef=None):
     """ValueError when the ``--moe-*`` flags are set for a tier without the routed FFN or together with
     ``--activation-recompute``; sets them on ``mcfg`` (whose ``validate`` refuses out-of-range values)."""
+    losses = " / ".join(flag for flag, v in (("--moe-aux-loss-coef", aux_coef), ("--moe-z-loss-coef", z_coef))
+                        if v is not None)
+    if losses and not mcfg.causal:
+        raise ValueError(f"{losses}: the router losses need --moe-experts on a causal tier (M7B, M7B_narrow, mtiny); "
+                         f"tier {tier} has the reference's dense GELU MLP")
     if experts is None:
         if top_k is not None or factor is not None:
             raise ValueError("--moe-top-k / --moe-capacity-factor are only used together with --moe-experts")
+        if losses:
+            raise ValueError(f"{losses}: only used together with --moe-experts")
         return
     if not mcfg.causal:
         raise ValueError(f"--moe-experts needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the "
@@ -228,6 +242,12 @@ def check_moe(experts, top_k, factor, recompute, mcfg, tier):
         mcfg.moe_top_k = top_k
     if factor is not None:
         mcfg.moe_capacity_factor = factor
+    for flag, name, v in (("--moe-aux-loss-coef", "moe_aux_loss_coef", aux_coef),
+                          ("--moe-z-loss-coef", "moe_z_loss_coef", z_coef)):
+        if v is not None:
+            if not 0.0 <= v < float("inf"):
+                raise ValueError(f"{flag} must be a finite number >= 0, got {v!r}")
+            setattr(mcfg, name, v)
     mcfg.validate()
 
 
@@ -294,7 +314,8 @@ def train(args):
         head_chunk = getattr(args, "head_chunk", None)
         check_head_chunk(head_chunk, mcfg, args.tier)
         check_moe(getattr(args, "moe_experts", None), getattr(args, "moe_top_k", None),
-                  getattr(args, "moe_capacity_factor", None), recompute, mcfg, args.tier)
+                  getattr(args, "moe_capacity_factor", None), recompute, mcfg, args.tier,
+                  getattr(args, "moe_aux_loss_coef", None), getattr(args, "moe_z_loss_coef", None))
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -315,7 +336,9 @@ def train(args):
             from .ops.ref import moe_capacity
             print(f"Mixture of experts: {mcfg.n_experts} experts, top-{mcfg.moe_top_k}, capacity "
                   f"{moe_capacity(head_rows, mcfg.n_experts, mcfg.moe_top_k, mcfg.moe_capacity_factor)} slots per "
-                  f"expert for the {head_rows} rows per micro-step (factor {mcfg.moe_capacity_factor})", flush=True)
+                  f"expert for the {head_rows} rows per micro-step (factor {mcfg.moe_capacity_factor}), "
+                  f"load-balancing loss coefficient {mcfg.moe_aux_loss_coef}, router z-loss coefficient "
+                  f"{mcfg.moe_z_loss_coef}", flush=True)
         cp = None
         if cp_n > 1:
             cp = _context.ContextParallel(cp_n, cp_layout, mcfg.sliding_window, world, rank)
@@ -472,7 +495,8 @@ def train(args):
             "context_parallel": cp_n, "cp_layout": cp_layout if cp_n > 1 else None,
             "activation_recompute": recompute,
             "head_chunk": head_chunk, "head_chunks": n_head_chunks,
-            # the last micro-step's assignments per layer and expert (before drops), read once, here
+            # the last micro-step's assignments per layer and expert (before drops) and, with an auxiliary router
+            # loss on, its per-layer values, read once, here
             "moe": model.moe_stats(head_rows) if mcfg.n_experts else None,
             "cp_ranges": (cp.describe(args.seq_len)["cp_ranges"] if cp is not None else None),
             "tokens_per_micro_step": tokens_step,
@@ -563,7 +587,8 @@ def main(argv=None):
         parser.error(str(e))
     try:
         check_moe(args.moe_experts, args.moe_top_k, args.moe_capacity_factor, args.activation_recompute,
-                  get_model_config(args.tier, args.seq_len), args.tier)
+                  get_model_config(args.tier, args.seq_len), args.tier, args.moe_aux_loss_coef,
+                  args.moe_z_loss_coef)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

@@ -45,6 +45,10 @@ class ModelConfig:
     n_experts: Optional[int] = None
     moe_top_k: int = 2
     moe_capacity_factor: float = 1.25
+    # auxiliary router losses, per layer on the rank's local token rows (ops/ref.py moe_aux_fwd):
+    # loss = lm_loss + moe_aux_loss_coef * sum_layers balance + moe_z_loss_coef * sum_layers z.  0 = off
+    moe_aux_loss_coef: float = 0.0
+    moe_z_loss_coef: float = 0.0
 
     def __post_init__(self):
         self.validate()
@@ -68,7 +72,14 @@ class ModelConfig:
             raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
         if isinstance(cf, bool) or not isinstance(cf, (int, float)) or not 0.0 < cf < float("inf"):
             raise ValueError(f"moe_capacity_factor must be a positive finite number, got {cf!r}")
+        for name in ("moe_aux_loss_coef", "moe_z_loss_coef"):
+            c = getattr(self, name)
+            if isinstance(c, bool) or not isinstance(c, (int, float)) or not 0.0 <= c < float("inf"):
+                raise ValueError(f"{name} must be a finite number >= 0, got {c!r}")
         ne = self.n_experts
+        if ne is None and self.moe_aux_on:
+            raise ValueError("moe_aux_loss_coef / moe_z_loss_coef need n_experts (the mixture-of-experts FFN of the "
+                             f"mistral arch), got n_experts None, arch {self.arch!r}")
         if ne is not None:
             if isinstance(ne, bool) or not isinstance(ne, int) or not 2 <= ne <= 64:
                 raise ValueError(f"n_experts must be an integer in [2, 64] or None, got {ne!r}")
@@ -80,6 +91,11 @@ class ModelConfig:
                 raise ValueError(f"n_experts needs n_embd to be a multiple of 64, got {self.n_embd}")
         elif self.arch != "mistral" and (k != 2 or cf != 1.25):
             raise ValueError(f"moe_top_k / moe_capacity_factor need the mistral arch, got arch {self.arch!r}")
+
+    @property
+    def moe_aux_on(self) -> bool:
+        """An auxiliary router loss is on: the layers return (balance, z) and the router gradient is dense."""
+        return bool(self.moe_aux_loss_coef or self.moe_z_loss_coef)
 
     @property
     def head_dim(self) -> int:

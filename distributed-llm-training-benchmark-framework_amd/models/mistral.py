@@ -19,6 +19,8 @@ run as dltb HIP kernels on the GPU.
 
 With ``cfg.n_experts`` the FFN is a top-k mixture of experts with a fixed capacity per expert (``_moe_fwd`` /
 ``_moe_bwd``, csrc/moe.hip): ``mlp`` then holds ``router.weight`` and ``experts.{e}.{gate_up_proj,down_proj}.weight``.
+With ``cfg.moe_aux_loss_coef`` / ``cfg.moe_z_loss_coef`` every layer also returns its (load-balancing, router-z) pair and
+the loss is ``lm_loss + a sum_layers balance + b sum_layers z`` (ops/ref.py ``moe_aux_fwd``), on the rank's local rows.
 """
 import math
 
@@ -191,9 +193,12 @@ class _LayerFn(torch.autograd.Function):
         a = F_.linear_fwd(o, wo)
         x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
         ctx.moe = None
+        router_losses = None
         if cfg.n_experts:       # top-k routed experts instead of the dense FFN; gu / hh are per expert, in ctx.moe
-            m, ctx.moe = _moe_fwd(model, i, h2, ws[4:])
+            m, ctx.moe, *rest = _moe_fwd(model, i, h2, ws[4:])
             gu = hh = None
+            if rest:            # the layer's (balance, z): a second, differentiable output (not kept on ctx)
+                router_losses = rest[0]
         else:
             wgu, wd = ws[4:]
             gu = F_.linear_fwd(h2, wgu)
@@ -208,10 +213,10 @@ class _LayerFn(torch.autograd.Function):
         elif ctx.recompute == "full":         # ... and everything else but the attention output
             ctx.saved = (x, None, None, None, o, lse, None, None, None, None, None, None)
         ctx.bounds = bounds
-        return x2
+        return x2 if router_losses is None else (x2, router_losses)
 
     @staticmethod
-    def backward(ctx, dx2):
+    def backward(ctx, dx2, daux=None):
         if ctx.recompute != "off":
             return _layer_backward_recompute(ctx, dx2), None, None
         model, i = ctx.model, ctx.i
@@ -226,7 +231,7 @@ class _LayerFn(torch.autograd.Function):
         dx2 = dx2.contiguous()
         s = [rt.grad_slot(unit, j) for j in range(len(ws))]
         if ctx.moe is not None:
-            dh2 = _moe_bwd(model, unit, dx2, h2, ws, s, ctx.moe)
+            dh2 = _moe_bwd(model, unit, dx2, h2, ws, s, ctx.moe, daux)
             ctx.moe = None
         else:
             wgu, wd = ws[4:]
@@ -266,12 +271,26 @@ def _moe_fwd(model, i, h2, ws):
     """The routed FFN of layer ``i`` on the rows ``h2`` [N, d]; ``ws``: the router, then (gate_up, down) per expert.
     Route (top-k, softmax gates), assign slots (fixed capacity C per expert, row-major order, overflow dropped),
     gather the rows into ``xe`` [E C, d], run each expert's SwiGLU FFN on its [C, d] slab with the dense path's
-    GEMM calls, and combine.  Every shape is static.  Returns (m, what the backward needs)."""
+    GEMM calls, and combine.  Every shape is static.  Returns (m, what the backward needs).  With an auxiliary loss
+    on (``cfg.moe_aux_on``) the backward's tuple has three more entries -- the router logits, their log-sum-exp and the
+    layer's own copy of the counts -- and a third value is returned: the [2] tensor (balance, z), which also goes to
+    row ``i`` of ``model.moe_aux``."""
     cfg = model.cfg
     E, K = cfg.n_experts, cfg.moe_top_k
     C = ref.moe_capacity(h2.shape[0], E, K, cfg.moe_capacity_factor)
-    expert, gate, _ = F_.moe_route(h2, ws[0], K)
-    slot, src, _, _ = F_.moe_assign(expert, E, C, model.moe_counts(h2.device)[i])
+    expert, gate, logits = F_.moe_route(h2, ws[0], K)
+    extra = ()
+    if cfg.moe_aux_on:
+        # the backward reads the counts again (f in moe_aux_bwd_), and the model's row i is overwritten by the next
+        # forward, which may come before this one's backward: the layer keeps a tensor of its own, at the price of one
+        # small copy launch that fills the model's row for the record
+        slot, src, _, counts = F_.moe_assign(expert, E, C)
+        model.moe_counts(h2.device)[i].copy_(counts)
+        lse, aux = F_.moe_aux_fwd(logits, counts, K, model.moe_aux(h2.device)[i])
+        extra = (logits, lse, counts)
+    else:
+        slot, src, _, _ = F_.moe_assign(expert, E, C, model.moe_counts(h2.device)[i])
+    del logits
     xe = F_.moe_dispatch(h2, src)
     ye = torch.empty_like(xe)
     gus, hhs = [], []
@@ -283,19 +302,28 @@ def _moe_fwd(model, i, h2, ws):
         gus.append(gu)
         hhs.append(hh)
     m = F_.moe_combine(ye, slot, gate)
-    return m, (expert, gate, slot, src, xe, ye, gus, hhs, C)
+    saved = (expert, gate, slot, src, xe, ye, gus, hhs, C) + extra
+    return (m, saved, aux) if extra else (m, saved)
 
 
-def _moe_bwd(model, unit, dm, h2, ws, s, saved):
+def _moe_bwd(model, unit, dm, h2, ws, s, saved, daux=None):
     """The backward of :func:`_moe_fwd`, in gather form throughout: returns dh2 and writes the router's and every
     expert's weight gradient into its slot (``ws`` / ``s``: the unit's parameters and gradient slots; the router is
     parameter 4, expert e's pair 5 + 2e and 6 + 2e).  An expert without tokens sees zero slabs, so its gradients
-    are exact zeros."""
+    are exact zeros.  ``daux``: the gradient of the layer's (balance, z) when an auxiliary loss is on; its term is
+    added to the dense dlogits before the router's two gradient kernels read them."""
     rt = model.rt
-    (expert, gate, slot, src, xe, ye, gus, hhs, C) = saved
+    (expert, gate, slot, src, xe, ye, gus, hhs, C) = saved[:9]
     E = model.cfg.n_experts
     dye, _, dlogits = F_.moe_combine_bwd(dm, ye, slot, src, expert, gate, E)
     del ye
+    dense = len(saved) > 9
+    if dense:
+        logits, lse, counts = saved[9:]
+        g = torch.zeros(2, dtype=logits.dtype, device=logits.device) if daux is None \
+            else daux.to(logits.dtype).contiguous()
+        F_.moe_aux_bwd_(dlogits, logits, lse, counts, g, model.cfg.moe_top_k)
+        del logits, lse, counts
     dxe = torch.empty_like(xe)
     for e in range(E):
         rows = slice(e * C, (e + 1) * C)
@@ -307,7 +335,7 @@ def _moe_bwd(model, unit, dm, h2, ws, s, saved):
         gus[e] = hhs[e] = None
         F_.linear_wgrad(dgu, xe[rows], s[ju][0], None, s[ju][1])
         dxe[rows].copy_(F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, ju, wgu)))
-    F_.moe_router_wgrad(dlogits, h2, s[4][0], s[4][1])
+    F_.moe_router_wgrad(dlogits, h2, s[4][0], s[4][1], dense=dense)
     return F_.moe_dispatch_bwd(dxe, slot, dlogits, ws[4])
 
 
@@ -548,6 +576,7 @@ class MistralLM(nn.Module):
         # them as dlogits for the backward; N keeps their log-sum-exp rows and re-runs the product per chunk
         self.head_chunk = None
         self._moe_counts = None     # int32 [n_layer, n_experts]: the last micro-step's assignments per expert
+        self._moe_aux = None        # fp32 [n_layer, 2]: the last micro-step's (balance, z) per layer (aux loss on)
         self.unit_embed = Unit("embed", [("model.embed_tokens.weight", self.model.embed_tokens.weight)], 0)
         self.unit_blocks = [Unit(f"layers.{i}", [(f"model.layers.{i}.{n}", p) for n, p in layer.param_list()], i + 1)
                             for i, layer in enumerate(self.model.layers)]
@@ -572,6 +601,13 @@ class MistralLM(nn.Module):
             self._moe_counts = torch.zeros(self.cfg.n_layer, self.cfg.n_experts, dtype=torch.int32, device=device)
         return self._moe_counts
 
+    def moe_aux(self, device):
+        """fp32 [n_layer, 2], row i = layer i's (load-balancing loss, router z-loss) of the last micro-step; written
+        only while ``cfg.moe_aux_on``."""
+        if self._moe_aux is None or self._moe_aux.device.type != torch.device(device).type:
+            self._moe_aux = torch.zeros(self.cfg.n_layer, 2, dtype=torch.float32, device=device)
+        return self._moe_aux
+
     def moe_stats(self, rows):
         """The ``moe`` block of the harness's extended record for micro-steps of ``rows`` local token rows: reads the
         last micro-step's counts (one device-to-host copy; call it after the timed steps).  The figures are the
@@ -582,12 +618,23 @@ class MistralLM(nn.Module):
         out = {"experts": E, "top_k": K, "capacity_factor": cfg.moe_capacity_factor, "capacity": C,
                "counts": None, "drop_fraction": None,
                "scope": "this rank's local token rows of the last micro-step (not summed over ranks): counts per "
-                        "layer and expert before drops; drop_fraction pooled over the layers"}
+                        "layer and expert before drops; drop_fraction pooled over the layers; balance_loss / z_loss "
+                        "per layer, unweighted (None when both coefficients are 0).  The reported training loss is "
+                        "the total: lm_loss + aux_loss_coef * sum(balance_loss) + z_loss_coef * sum(z_loss)",
+               "aux_loss_coef": cfg.moe_aux_loss_coef, "z_loss_coef": cfg.moe_z_loss_coef,
+               "balance_loss": None, "z_loss": None}
         if self._moe_counts is not None:
-            counts = self._moe_counts.cpu()
+            aux_on = cfg.moe_aux_on and self._moe_aux is not None
+            # one device-to-host copy: the counts and, as fp32 bit patterns beside them, the two losses
+            both = self._moe_counts if not aux_on else torch.cat([self._moe_counts, self._moe_aux.view(torch.int32)], 1)
+            both = both.cpu()
+            counts = both[:, :E]
             out["counts"] = counts.tolist()
             total = int(counts.sum())
             out["drop_fraction"] = float((counts - C).clamp(min=0).sum()) / total if total else 0.0
+            if aux_on:
+                aux = both[:, E:].contiguous().view(torch.float32)
+                out["balance_loss"], out["z_loss"] = aux[:, 0].tolist(), aux[:, 1].tolist()
         return out
 
     def forward(self, idx, targets=None, return_logits=False):
@@ -610,9 +657,19 @@ class MistralLM(nn.Module):
         self._cur_bt = (B, T)
         anchor = torch.empty((), requires_grad=True)
         x = _EmbedFn.apply(anchor, idx, self)
+        auxs = []
         for i in range(len(self.unit_blocks)):
             x = _LayerFn.apply(x, self, i)
+            if isinstance(x, tuple):        # an auxiliary router loss is on: (x, the layer's (balance, z))
+                x, aux = x
+                auxs.append(aux)
         logits, loss = _HeadFn.apply(x, self, targets, return_logits)
         if targets is None:
             return logits.view(B, T, -1), None
+        if auxs:        # a fixed number of small launches whatever the depth, nothing read by the host
+            tot = torch.stack(auxs).sum(0).to(loss.dtype)
+            if self.cfg.moe_aux_loss_coef:
+                loss = loss + self.cfg.moe_aux_loss_coef * tot[0]
+            if self.cfg.moe_z_loss_coef:
+                loss = loss + self.cfg.moe_z_loss_coef * tot[1]
         return (logits.view(B, T, -1) if return_logits else None), loss

@@ -96,6 +96,21 @@ def _moe_ffn(mlp, h, cfg):
     return out
 
 
+def _moe_aux_loss(mlp, h, cfg):
+    """The layer's ``a * balance + b * z`` (``cfg.moe_aux_loss_coef`` / ``cfg.moe_z_loss_coef``) on the rows ``h`` in
+    stock ops, differentiated by autograd alone: balance = E sum_e f[e] mean_n softmax(logits)[n, e] with f, the
+    fraction of the N K assignments that chose expert e (before drops), detached; z = mean_n logsumexp(logits)^2."""
+    N = h.shape[0]
+    E, K = cfg.n_experts, cfg.moe_top_k
+    logits = mlp.router(h)
+    idx = torch.sort(logits, dim=-1, descending=True, stable=True).indices[:, :K]
+    counts = torch.bincount(idx.reshape(-1), minlength=E)
+    f = (counts.to(logits.dtype) / (N * K)).detach()
+    balance = E * (f * torch.softmax(logits, -1).mean(0)).sum()
+    z = torch.logsumexp(logits, -1).pow(2).mean()
+    return cfg.moe_aux_loss_coef * balance + cfg.moe_z_loss_coef * z
+
+
 class OracleMistral(nn.Module):
     """Stock-op Mistral-shape decoder with the same parameter names as dltb.models.mistral."""
 
@@ -139,6 +154,7 @@ class OracleMistral(nn.Module):
         cos = ang.cos().float().to(idx.device)[None, None]
         sin = ang.sin().float().to(idx.device)[None, None]
         x = self.model.embed_tokens(idx)
+        aux = []
         for layer in self.model.layers:
             h = layer.input_layernorm(x)
             qkv = layer.self_attn.qkv_proj(h)
@@ -163,7 +179,10 @@ class OracleMistral(nn.Module):
                 o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
             x = x + layer.self_attn.o_proj(o.transpose(1, 2).reshape(B, T, H * hd))
             if cfg.n_experts:
-                x = x + _moe_ffn(layer.mlp, layer.post_attention_layernorm(x).reshape(B * T, -1), cfg).view_as(x)
+                h2 = layer.post_attention_layernorm(x).reshape(B * T, -1)
+                if cfg.moe_aux_loss_coef or cfg.moe_z_loss_coef:
+                    aux.append(_moe_aux_loss(layer.mlp, h2, cfg))
+                x = x + _moe_ffn(layer.mlp, h2, cfg).view_as(x)
                 continue
             gu = layer.mlp.gate_up_proj(layer.post_attention_layernorm(x))
             g, u = gu.chunk(2, -1)
@@ -172,4 +191,6 @@ class OracleMistral(nn.Module):
         loss = None
         if targets is not None:
             loss = F.cross_entropy(logits.view(-1, logits.size(-1)), targets.view(-1), ignore_index=-1)
+            for term in aux:
+                loss = loss + term
         return logits, loss

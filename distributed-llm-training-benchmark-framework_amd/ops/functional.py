@@ -406,12 +406,37 @@ def moe_dispatch_bwd(dxe, slot, dlogits, wr):
     return ref.moe_dispatch_bwd(dxe, slot, dlogits, wr)
 
 
-def moe_router_wgrad(dlogits, h, dwr, accumulate):
-    """dWr (+)= dlogits^T h into the router's gradient slot (fixed-order two-stage column reduction)."""
+def moe_router_wgrad(dlogits, h, dwr, accumulate, dense=False):
+    """dWr (+)= dlogits^T h into the router's gradient slot (fixed-order two-stage column reduction).  ``dense``:
+    the kernel for a ``dlogits`` without zeros (an auxiliary loss is on): 8 experts per pass over ``h``; the default
+    kernel reads only the rows with a non-zero entry, once per expert."""
     if _gpu(h):
-        ext().moe_router_wgrad(dlogits, h, dwr, bool(accumulate))
+        ext().moe_router_wgrad(dlogits, h, dwr, bool(accumulate), bool(dense))
     else:
-        ref.moe_router_wgrad(dlogits, h, dwr, accumulate)
+        ref.moe_router_wgrad(dlogits, h, dwr, accumulate, dense)
+
+
+def moe_aux_fwd(logits, counts, K, stats_out=None):
+    """(lse f32 [N], out f32 [2] = (load-balancing loss, router z-loss)) of the router logits and the per-expert
+    assignment counts (definitions: ref.py).  ``stats_out``: a contiguous [2] tensor that receives ``out`` as well
+    (the model's per-layer row, read by the harness after the run).  Two launches, no host read."""
+    if _gpu(logits):
+        lse, out = ext().moe_aux_fwd(logits, counts, K, stats_out)
+        return lse, out
+    lse, out = ref.moe_aux_fwd(logits, counts, K)
+    if stats_out is not None:
+        stats_out.copy_(out.detach())
+    return lse, out
+
+
+def moe_aux_bwd_(dlogits, logits, lse, counts, g, K):
+    """Adds the gradient of ``g[0] * balance + g[1] * z`` to the dense ``dlogits`` in place (``g``: a [2] tensor on
+    the device; softmax recomputed from ``logits`` and ``lse``)."""
+    if _gpu(logits):
+        ext().moe_aux_bwd_(dlogits, logits, lse, counts, g, K)
+    else:
+        ref.moe_aux_bwd_(dlogits, logits, lse, counts, g, K)
+    return dlogits
 
 
 def rope_(qkv2d, cos, sin, T, heads, D, inverse=False):

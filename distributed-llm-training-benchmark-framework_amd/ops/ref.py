@@ -472,8 +472,37 @@ def moe_dispatch_bwd(dxe, slot, dlogits, wr):
     return (acc + dlogits.to(x.dtype) @ _f(wr).to(x.dtype)).to(dxe.dtype)
 
 
-def moe_router_wgrad(dlogits, h, dwr, accumulate):
-    """dWr (+)= dlogits^T h into the router's gradient slot."""
+def moe_aux_fwd(logits, counts, K):
+    """(lse [N], out [2] = (balance, z)) of the router's ``logits`` [N, E] and the assignment ``counts`` [E] (before
+    drops) of K choices per token.  With p = softmax(logits) over all E experts and lse = logsumexp(logits) (row
+    maximum subtracted): f[e] = counts[e] / (N K), a constant; P[e] = mean_n p[n, e];
+    balance = E sum_e f[e] P[e] (1 for a uniform router, towards E as it collapses onto one expert);
+    z = mean_n lse[n]^2."""
+    N, E = logits.shape
+    mx = logits.max(-1, keepdim=True).values
+    ex = torch.exp(logits - mx)
+    s = ex.sum(-1, keepdim=True)
+    lse = (mx + torch.log(s)).squeeze(-1)
+    f = counts.to(logits.dtype) / float(N * K)
+    balance = E * (f * ((ex / s).sum(0) / N)).sum()
+    z = (lse * lse).sum() / N
+    return lse, torch.stack([balance, z])
+
+
+def moe_aux_bwd_(dlogits, logits, lse, counts, g, K):
+    """dlogits[n, e] += g_b (E / N) p[n, e] (f[e] - sum_j f[j] p[n, j]) + g_z (2 / N) lse[n] p[n, e] in place, with
+    p = exp(logits - lse) and ``g`` = (g_b, g_z), the incoming gradients of :func:`moe_aux_fwd`'s (balance, z)."""
+    N, E = logits.shape
+    p = torch.exp(logits - lse[:, None])
+    f = counts.to(logits.dtype) / float(N * K)
+    g = g.to(logits.dtype)
+    dot = (f * p).sum(-1, keepdim=True)
+    dlogits += g[0] * (E / N) * (p * (f - dot)) + g[1] * (2.0 / N) * (lse[:, None] * p)
+    return dlogits
+
+
+def moe_router_wgrad(dlogits, h, dwr, accumulate, dense=False):
+    """dWr (+)= dlogits^T h into the router's gradient slot.  ``dense``: which kernel the GPU runs (nothing here)."""
     h32 = _f(h)
     v = dlogits.to(h32.dtype).t() @ h32
     if accumulate:

@@ -2,6 +2,7 @@
 """What the top-k mixture-of-experts FFN costs on one MI355X (writes profiles/moe_layer.txt).
 
     python scripts/bench_moe.py [--out profiles/moe_layer.txt] [--rows 4096,16384] [--factors 1.0,1.25,2.0] [--reps 9]
+    python scripts/bench_moe.py --aux-loss-coef 0.01 --z-loss-coef 0.001      (appends to the same file)
 
 Times the FFN part of one MoE layer at the M7B shape (d 4096, f 14336, E 8, K 2), forward plus backward: route,
 assign, dispatch, the E experts, combine and their backward (``models/mistral.py::_moe_fwd`` / ``_moe_bwd``).  The
@@ -11,6 +12,13 @@ kernels are also timed one by one on the same tensors, and so are the 2 E slab c
 output and data gradient is copied into its rows of the slot buffer); kernels plus copies over the layer's time is the
 share the routing takes beside the GEMMs and SwiGLU kernels.  The drop fraction is that of the random-init router on
 normal rows.
+
+With ``--aux-loss-coef`` / ``--z-loss-coef`` the script measures what the auxiliary router losses cost instead, at the
+same shapes, and appends to the file: the same layer (same weights, same rows) forward plus backward with the
+coefficients set against both at 0, interleaved rep by rep, and the router's weight gradient on a ``dlogits`` without
+zeros through the sparse kernel (the default) and the dense one (``dense=True``, what the layer runs with a loss on):
+batches of calls per event pair, the two kernels interleaved, once with the rows hot in the caches and once walking
+a ring of copies larger than the caches.
 """
 import argparse
 import os
@@ -41,6 +49,8 @@ def main():
     ap.add_argument("--experts", type=int, default=8)
     ap.add_argument("--top-k", type=int, default=2)
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--aux-loss-coef", type=float, default=0.0, help="load-balancing loss coefficient (0: off)")
+    ap.add_argument("--z-loss-coef", type=float, default=0.0, help="router z-loss coefficient (0: off)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_moe.py measures on the GPU; none found")
@@ -71,6 +81,8 @@ def main():
         m.rt = ParamRuntime()
         return m
 
+    if a.aux_loss_coef or a.z_loss_coef:
+        return aux_section(a, layer, F_, mistral, d, f, E, K, dev, dt)
     dense = layer(None, K * f, 1.0)
     du = dense.unit_blocks[0]
     dws = dense.rt.acquire(du)
@@ -145,6 +157,85 @@ def main():
     with open(a.out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     print(f"wrote {a.out}")
+
+
+WG_BATCH = 20        # router weight-gradient calls per event pair (one call is tens of microseconds)
+WG_RING_MB = 768     # the cold ring: three times the MI355X's 256 MB Infinity Cache
+
+
+def aux_section(a, layer, F_, mistral, d, f, E, K, dev, dt):
+    """The layer with the auxiliary losses against the same layer without, and the two router weight-gradient kernels
+    on a dense dlogits; appended to ``a.out``."""
+    lines = [f"# scripts/bench_moe.py --aux-loss-coef {a.aux_loss_coef} --z-loss-coef {a.z_loss_coef} on "
+             f"{torch.cuda.get_device_name(0)}, torch {torch.__version__}",
+             f"# one layer's FFN part, forward + backward, bf16, d {d}, f {f}, E {E}, K {K}: the same weights and rows "
+             "with the coefficients set and with both 0",
+             f"# medians of {a.reps} interleaved reps after 3 warm-up reps; ms",
+             "rows factor moe_ms_coef0 moe_ms_with_losses ratio"]
+    wg = ["# router weight gradient on a dlogits without zeros: the sparse kernel (default) and the dense one; ms per "
+          f"call from {WG_BATCH} calls per event pair, the two kernels' batches interleaved, medians of {a.reps} reps.",
+          "# hot: every call reads the same h (it stays in L2 / Infinity Cache, so the rates are above HBM's); cold: the "
+          f"calls walk a ring of copies of h of at least {WG_RING_MB} MB, so every read comes from HBM",
+          f"# {torch.cuda.get_device_name(0)!r} is how torch names the device here",
+          "rows experts d hot_sparse_ms hot_dense_ms hot_dense_over_sparse cold_sparse_ms cold_dense_ms "
+          "cold_dense_over_sparse"]
+    daux = torch.tensor([a.aux_loss_coef, a.z_loss_coef], device=dev)
+    for rows in [int(r) for r in a.rows.split(",")]:
+        h = torch.randn(rows, d, device=dev).to(dt)
+        dm = torch.randn(rows, d, device=dev).to(dt)
+        for factor in [float(x) for x in a.factors.split(",")]:
+            moe = layer(E, f, factor)
+            mu = moe.unit_blocks[0]
+            mws = moe.rt.acquire(mu)
+            ms = [(torch.empty_like(w), False) for w in mws]
+
+            def step(on):
+                moe.cfg.moe_aux_loss_coef = a.aux_loss_coef if on else 0.0
+                moe.cfg.moe_z_loss_coef = a.z_loss_coef if on else 0.0
+                saved = mistral._moe_fwd(moe, 0, h, mws[4:])[1]
+                return mistral._moe_bwd(moe, mu, dm, h, mws, ms, saved, daux if on else None)
+
+            t_off, t_on = [], []
+            for rep_ in range(a.reps + 3):
+                t0, _ = _timed(lambda: step(False))
+                t1, _ = _timed(lambda: step(True))
+                if rep_ >= 3:
+                    t_off.append(t0)
+                    t_on.append(t1)
+            m0, m1 = statistics.median(t_off), statistics.median(t_on)
+            lines.append(f"{rows} {factor} {m0:.3f} {m1:.3f} {m1 / m0:.4f}")
+            print(lines[-1], flush=True)
+            wr = mws[4]
+            del moe, mws, ms
+            torch.cuda.empty_cache()
+        dl = torch.randn(rows, E, device=dev)
+        dwr = torch.empty_like(wr)
+        n_ring = max(2, -(-WG_RING_MB * (1 << 20) // (h.numel() * h.element_size())))
+        ring = [h] + [h.clone() for _ in range(n_ring - 1)]
+        row = f"{rows} {E} {d}"
+        for hs in ([h], ring):
+
+            def batch(dense):
+                for j in range(WG_BATCH):
+                    F_.moe_router_wgrad(dl, hs[j % len(hs)], dwr, False, dense=dense)
+
+            ts = ([], [])
+            for rep_ in range(a.reps + 2):
+                for dense in (False, True):
+                    t = _timed(lambda: batch(dense))[0] / WG_BATCH
+                    if rep_ >= 2:
+                        ts[dense].append(t)
+            sp, de = statistics.median(ts[0]), statistics.median(ts[1])
+            row += f" {sp:.4f} {de:.4f} {de / sp:.3f}"
+        del ring
+        torch.cuda.empty_cache()
+        wg.append(row)
+        print(wg[-1], flush=True)
+    lines += wg + [f"# written {time.strftime('%Y-%m-%d')}"]
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print(f"appended to {a.out}")
 
 
 if __name__ == "__main__":

@@ -107,6 +107,7 @@ def run_case(name, spec, world, rank, device, a):
     if a.moe_experts is not None and mcfg.arch == "mistral":      # the Mistral-shape cases only
         mcfg.n_experts, mcfg.moe_top_k = a.moe_experts, a.moe_top_k
         mcfg.moe_capacity_factor = a.moe_capacity_factor
+        mcfg.moe_aux_loss_coef, mcfg.moe_z_loss_coef = a.moe_aux_loss_coef, a.moe_z_loss_coef
     mcfg.validate()
     with torch.device(device):
         model = build_model(mcfg)
@@ -189,6 +190,8 @@ def main():
                     help="experts per layer of the Mistral-shape cases (models/mistral.py); default: the dense FFN")
     ap.add_argument("--moe-top-k", type=int, default=2)
     ap.add_argument("--moe-capacity-factor", type=float, default=1.25)
+    ap.add_argument("--moe-aux-loss-coef", type=float, default=0.0, help="with --moe-experts: load-balancing loss")
+    ap.add_argument("--moe-z-loss-coef", type=float, default=0.0, help="with --moe-experts: router z-loss")
     a = ap.parse_args()
     from dltb.utils.dist import cleanup_distributed, setup_distributed
     world = int(os.environ.get("WORLD_SIZE", "1"))
