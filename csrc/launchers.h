@@ -172,6 +172,11 @@ void dltb_moe_route(const void* h, const void* wr, int* expert, float* gate, flo
 // scratch: int32 [2][ceil(N K / 64)][E]
 void dltb_moe_assign(const int* expert, int* scratch, int* slot, int* src, int* src_k, int* counts, int N, int K,
                      int E, int C, hipStream_t st);
+// dropless: the packed layout of rows = dltb_moe_dropless_rows(N, K, E) = roundup(N K, 128) + 128 E slot rows;
+// offsets [E + 1] = exclusive prefix sum of the counts rounded up to 128; src / src_k [rows]; same scratch
+int dltb_moe_dropless_rows(int N, int K, int E);
+void dltb_moe_assign_dropless(const int* expert, int* scratch, int* slot, int* src, int* src_k, int* counts,
+                              int* offsets, int N, int K, int E, int rows, hipStream_t st);
 void dltb_moe_dispatch(const void* h, const int* src, void* xe, int rows, int N, int d, hipStream_t st);
 void dltb_moe_combine(const void* ye, const int* slot, const float* gate, void* m, int N, int d, int K, int rows,
                       hipStream_t st);
@@ -200,6 +205,20 @@ bool dltb_gemm_supported(int M, int N, int K, bool tn, int cfg);
 int dltb_gemm(const void* a, const void* b, void* c, const void* bias, float* part, long lda, long ldb,
               long ldc, int M, int N, int K, bool tn, int accumulate, int splits, int cfg, int pf, int gm,
               const float* alpha, hipStream_t st, int stages = 0);
+
+// ---- gemm_grouped.hip: one launch over E <= 64 row segments [offsets[e], offsets[e + 1]) of [0, R) (int32 on the
+// device, multiples of 128, offsets[E] <= R); R, M, N multiples of 128, K of 64; 16-byte aligned operand rows,
+// 16-byte aligned outputs; return 0, or -1 when refused.
+//   NT: c[r, :] = a[r, :] B_e^T for r in segment e (a [R][K], B_e = b[e] [N][K], c [R][N]); rows past offsets[E]: 0
+//   TN: dW_e (+)= dy[segment e]^T x[segment e] (dy [R][M], x [R][N], dW_e = dw[e] [M][N] contiguous); bit e of
+//       `accumulate`: += ; an empty segment writes zeros, or nothing when accumulating
+bool dltb_gemm_grouped_nt_supported(int R, int N, int K, int E);
+int dltb_gemm_grouped_nt(const void* a, const int* offsets, const void* const* b, void* c, long lda, long ldb,
+                         long ldc, int R, int N, int K, int E, hipStream_t st);
+bool dltb_gemm_grouped_tn_supported(int R, int M, int N, int E);
+int dltb_gemm_grouped_tn(const void* dy, const void* x, const int* offsets, void* const* dw,
+                         unsigned long long accumulate, long lddy, long ldx, int R, int M, int N, int E,
+                         hipStream_t st);
 
 // ---- gemm_nn.hip: C[M,N] = alpha A B; A [M][K], B [K][N] (the tied head's dgrad without a transposed W);
 // cfg 0 = 128x128, 1 = 256x128, 2 = 64x64 tiles; returns the split count used, -1 when refused

@@ -7,6 +7,9 @@
 //   moe_assign        slot of every (token, choice) in row-major order: per-wave expert histograms (ballots),
 //                     one block scanning them per expert, then positions; position >= C is dropped (-1).
 //                     Writes the inverse too: src / src_k of every slot (-1 when the slot stays empty)
+//   moe_assign_dropless  the same order without a capacity: expert e's assignments fill a 128-aligned segment of
+//                     one packed [R] row space (R static), the bounds written to offsets [E + 1] for the grouped
+//                     GEMMs (gemm_grouped.hip); nothing is dropped, unreached rows get src = -1
 //   moe_dispatch      xe[slot] = h[src[slot]]; empty slots are zero rows
 //   moe_combine       m[n] = sum_k gate[n, k] ye[slot[n, k]], fp32 in k order, rounded once
 //   moe_combine_bwd   dye[slot] = gate dm[src], dgate = <dm, ye[slot]>, and the softmax backward into a dense
@@ -183,6 +186,59 @@ __global__ __launch_bounds__(256) void moe_place_kernel(const int* __restrict__ 
     const int p = base[(size_t)w * E + e] + rank;
     if (p < C) {
       s = e * C + p;
+      src[s] = i / K;
+      src_k[s] = i % K;
+    }
+  }
+  slot[i] = s;
+}
+
+// Dropless placement into the packed layout: expert e owns the rows [offsets[e], offsets[e + 1]), offsets = the
+// exclusive prefix sum of the counts rounded up to SEG rows, and assignment (n, k) at position p of its expert gets
+// row offsets[e] + p, whatever p is.  Every block rebuilds the E + 1 offsets from the counts in LDS (block 0 writes
+// them out); rows [0, rows) no assignment reaches -- a segment's padding and the tail past offsets[E] -- get -1.
+constexpr int SEG = 128;    // segment granularity: the grouped GEMMs' tile rows (gemm_grouped.hip)
+
+__global__ __launch_bounds__(256) void moe_place_dropless_kernel(const int* __restrict__ expert,
+                                                                 const int* __restrict__ base,
+                                                                 const int* __restrict__ counts, int* __restrict__ slot,
+                                                                 int* __restrict__ src, int* __restrict__ src_k,
+                                                                 int* __restrict__ offsets, int NK, int K, int E,
+                                                                 int rows) {
+  __shared__ int off[65], cnt[64];
+  const int lane = threadIdx.x & 63;
+  if (threadIdx.x <= E) {                      // E <= 64 serial adds per thread: the scan of a 64-entry table
+    int run = 0;
+    for (int x = 0; x < (int)threadIdx.x; ++x) run += (counts[x] + SEG - 1) / SEG * SEG;
+    off[threadIdx.x] = run;
+    if (threadIdx.x < E) cnt[threadIdx.x] = counts[threadIdx.x];
+    if (blockIdx.x == 0) offsets[threadIdx.x] = run;
+  }
+  __syncthreads();
+  DLTB_DCHECK(off[E] <= rows);
+  for (int g = blockIdx.x * 256 + threadIdx.x; g < rows; g += gridDim.x * 256) {
+    bool filled = false;                       // disjoint from the rows written below
+    for (int x = 0; x < E; ++x) filled |= g >= off[x] && g < off[x] + cnt[x];
+    if (!filled) {
+      src[g] = -1;
+      src_k[g] = -1;
+    }
+  }
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w * 64 >= NK) return;
+  const int i = w * 64 + lane;
+  const int e = i < NK ? expert[i] : -1;
+  int rank = 0;
+  for (int x = 0; x < E; ++x) {
+    const unsigned long long b = __ballot(e == x);
+    if (e == x) rank = __popcll(b & ((1ull << lane) - 1ull));
+  }
+  if (i >= NK) return;
+  int s = -1;
+  if ((unsigned)e < (unsigned)E) {
+    const int p = off[e] + base[(size_t)w * E + e] + rank;
+    if (p < rows) {                            // always, for counts that sum to NK (rows >= NK + 127 E)
+      s = p;
       src[s] = i / K;
       src_k[s] = i % K;
     }
@@ -393,6 +449,20 @@ void dltb_moe_assign(const int* expert, int* scratch, int* slot, int* src, int* 
   hipLaunchKernelGGL(moe_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)wavecnt, base, counts, W, E);
   hipLaunchKernelGGL(moe_place_kernel, dim3(cdiv(W, 4)), dim3(256), 0, st, expert, (const int*)base,
                      (const int*)counts, slot, src, src_k, NK, K, E, C);
+}
+
+int dltb_moe_dropless_rows(int N, int K, int E) { return (N * K + SEG - 1) / SEG * SEG + SEG * E; }
+
+void dltb_moe_assign_dropless(const int* expert, int* scratch, int* slot, int* src, int* src_k, int* counts,
+                              int* offsets, int N, int K, int E, int rows, hipStream_t st) {
+  const int NK = N * K;
+  const int W = cdiv(NK, 64);
+  int* wavecnt = scratch;                     // [W][E]
+  int* base = scratch + (size_t)W * E;        // [W][E]
+  hipLaunchKernelGGL(moe_hist_kernel, dim3(cdiv(W, 4)), dim3(256), 0, st, expert, wavecnt, NK, E);
+  hipLaunchKernelGGL(moe_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)wavecnt, base, counts, W, E);
+  hipLaunchKernelGGL(moe_place_dropless_kernel, dim3(cdiv(W, 4)), dim3(256), 0, st, expert, (const int*)base,
+                     (const int*)counts, slot, src, src_k, offsets, NK, K, E, rows);
 }
 
 void dltb_moe_dispatch(const void* h, const int* src, void* xe, int rows, int N, int d, hipStream_t st) {

@@ -15,7 +15,7 @@ Differences that make the numbers honest (recorded in the extended sidecar):
 Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device, --bucket-mb, --dropout, --seed,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
 --doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk, --moe-experts, --moe-top-k,
---moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef.
+--moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef, --moe-dropless.
 """
 import argparse
 import json
@@ -99,6 +99,10 @@ def build_parser():
     p.add_argument("--moe-z-loss-coef", type=float, default=None, metavar="B",
                    help="with --moe-experts: add B times the router z-loss mean(logsumexp(logits)^2) of every layer "
                         "to the loss; default 0: off")
+    p.add_argument("--moe-dropless", action="store_true",
+                   help="with --moe-experts: no capacity, every assignment is kept; the experts' rows are packed into "
+                        "128-aligned segments of roundup(rows * K, 128) + 128 * E slot rows and run as grouped GEMMs "
+                        "(not together with --moe-capacity-factor); default: the fixed-capacity path")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -218,9 +222,18 @@ def check_head_chunk(n, mcfg, tier):
         raise ValueError(f"--head-chunk must be a positive multiple of 16, got {n}")
 
 
-def check_moe(experts, top_k, factor, recompute, mcfg, tier, aux_coef=None, z_coef=None):
+def check_moe(experts, top_k, factor, recompute, mcfg, tier, aux_coef=None, z_coef=None, dropless=False):
     """ValueError when the ``--moe-*`` flags are set for a tier without the routed FFN or together with
-    ``--activation-recompute``; sets them on ``mcfg`` (whose ``validate`` refuses out-of-range values)."""
+    ``--activation-recompute``, or ``--moe-dropless`` together with an explicit ``--moe-capacity-factor``; sets them
+    on ``mcfg`` (whose ``validate`` refuses out-of-range values)."""
+    if dropless:
+        if not mcfg.causal:
+            raise ValueError(f"--moe-dropless needs --moe-experts on a causal tier (M7B, M7B_narrow, mtiny); tier "
+                             f"{tier} has the reference's dense GELU MLP")
+        if experts is None:
+            raise ValueError("--moe-dropless is only used together with --moe-experts")
+        if factor is not None:
+            raise ValueError(f"--moe-dropless has no capacity: --moe-capacity-factor {factor} cannot be given with it")
     losses = " / ".join(flag for flag, v in (("--moe-aux-loss-coef", aux_coef), ("--moe-z-loss-coef", z_coef))
                         if v is not None)
     if losses and not mcfg.causal:
@@ -242,6 +255,8 @@ def check_moe(experts, top_k, factor, recompute, mcfg, tier, aux_coef=None, z_co
         mcfg.moe_top_k = top_k
     if factor is not None:
         mcfg.moe_capacity_factor = factor
+    if dropless:
+        mcfg.moe_dropless = True
     for flag, name, v in (("--moe-aux-loss-coef", "moe_aux_loss_coef", aux_coef),
                           ("--moe-z-loss-coef", "moe_z_loss_coef", z_coef)):
         if v is not None:
@@ -315,7 +330,8 @@ def train(args):
         check_head_chunk(head_chunk, mcfg, args.tier)
         check_moe(getattr(args, "moe_experts", None), getattr(args, "moe_top_k", None),
                   getattr(args, "moe_capacity_factor", None), recompute, mcfg, args.tier,
-                  getattr(args, "moe_aux_loss_coef", None), getattr(args, "moe_z_loss_coef", None))
+                  getattr(args, "moe_aux_loss_coef", None), getattr(args, "moe_z_loss_coef", None),
+                  bool(getattr(args, "moe_dropless", False)))
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -332,7 +348,13 @@ def train(args):
                 print(f"Head chunk: {head_chunk} rows, {n_head_chunks} chunk(s) of the {head_rows} rows per micro-step"
                       + ("" if n_head_chunks > 1 else " (one chunk holds them all: the unchunked head runs)"),
                       flush=True)
-        if mcfg.n_experts and is_main:
+        if mcfg.n_experts and mcfg.moe_dropless and is_main:
+            from .ops.ref import moe_dropless_rows
+            print(f"Mixture of experts: {mcfg.n_experts} experts, top-{mcfg.moe_top_k}, dropless: "
+                  f"{moe_dropless_rows(head_rows, mcfg.n_experts, mcfg.moe_top_k)} packed slot rows (R) for the "
+                  f"{head_rows} rows per micro-step, grouped GEMMs, load-balancing loss coefficient "
+                  f"{mcfg.moe_aux_loss_coef}, router z-loss coefficient {mcfg.moe_z_loss_coef}", flush=True)
+        elif mcfg.n_experts and is_main:
             from .ops.ref import moe_capacity
             print(f"Mixture of experts: {mcfg.n_experts} experts, top-{mcfg.moe_top_k}, capacity "
                   f"{moe_capacity(head_rows, mcfg.n_experts, mcfg.moe_top_k, mcfg.moe_capacity_factor)} slots per "
@@ -588,7 +610,7 @@ def main(argv=None):
     try:
         check_moe(args.moe_experts, args.moe_top_k, args.moe_capacity_factor, args.activation_recompute,
                   get_model_config(args.tier, args.seq_len), args.tier, args.moe_aux_loss_coef,
-                  args.moe_z_loss_coef)
+                  args.moe_z_loss_coef, args.moe_dropless)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

@@ -49,6 +49,10 @@ class ModelConfig:
     # loss = lm_loss + moe_aux_loss_coef * sum_layers balance + moe_z_loss_coef * sum_layers z.  0 = off
     moe_aux_loss_coef: float = 0.0
     moe_z_loss_coef: float = 0.0
+    # dropless routing: no capacity, every assignment kept.  The experts' rows are packed into 128-aligned segments of
+    # one [R, d] buffer, R = roundup(rows * moe_top_k, 128) + 128 * n_experts, and run as grouped GEMMs that read the
+    # segment bounds on the device (csrc/gemm_grouped.hip); moe_capacity_factor is not used.
+    moe_dropless: bool = False
 
     def __post_init__(self):
         self.validate()
@@ -77,6 +81,15 @@ class ModelConfig:
             if isinstance(c, bool) or not isinstance(c, (int, float)) or not 0.0 <= c < float("inf"):
                 raise ValueError(f"{name} must be a finite number >= 0, got {c!r}")
         ne = self.n_experts
+        if not isinstance(self.moe_dropless, bool):
+            raise ValueError(f"moe_dropless must be a bool, got {self.moe_dropless!r}")
+        if self.moe_dropless:
+            if ne is None or self.arch != "mistral":
+                raise ValueError("moe_dropless needs n_experts (the mixture-of-experts FFN of the mistral arch), got "
+                                 f"n_experts {ne!r}, arch {self.arch!r}")
+            if self.n_embd % 128 or self.ffn_dim % 128:
+                raise ValueError("moe_dropless needs n_embd and ffn_hidden to be multiples of 128 (the grouped GEMM's "
+                                 f"tile), got n_embd {self.n_embd}, ffn_hidden {self.ffn_dim}")
         if ne is None and self.moe_aux_on:
             raise ValueError("moe_aux_loss_coef / moe_z_loss_coef need n_experts (the mixture-of-experts FFN of the "
                              f"mistral arch), got n_experts None, arch {self.arch!r}")

@@ -21,6 +21,8 @@ With ``cfg.n_experts`` the FFN is a top-k mixture of experts with a fixed capaci
 ``_moe_bwd``, csrc/moe.hip): ``mlp`` then holds ``router.weight`` and ``experts.{e}.{gate_up_proj,down_proj}.weight``.
 With ``cfg.moe_aux_loss_coef`` / ``cfg.moe_z_loss_coef`` every layer also returns its (load-balancing, router-z) pair and
 the loss is ``lm_loss + a sum_layers balance + b sum_layers z`` (ops/ref.py ``moe_aux_fwd``), on the rank's local rows.
+With ``cfg.moe_dropless`` there is no capacity: the experts' rows are packed into 128-aligned segments and run as
+grouped GEMMs that read the segment bounds on the device (``_moe_fwd_dropless``, csrc/gemm_grouped.hip).
 """
 import math
 
@@ -276,6 +278,8 @@ def _moe_fwd(model, i, h2, ws):
     layer's own copy of the counts -- and a third value is returned: the [2] tensor (balance, z), which also goes to
     row ``i`` of ``model.moe_aux``."""
     cfg = model.cfg
+    if cfg.moe_dropless:
+        return _moe_fwd_dropless(model, i, h2, ws)
     E, K = cfg.n_experts, cfg.moe_top_k
     C = ref.moe_capacity(h2.shape[0], E, K, cfg.moe_capacity_factor)
     expert, gate, logits = F_.moe_route(h2, ws[0], K)
@@ -324,6 +328,10 @@ def _moe_bwd(model, unit, dm, h2, ws, s, saved, daux=None):
             else daux.to(logits.dtype).contiguous()
         F_.moe_aux_bwd_(dlogits, logits, lse, counts, g, model.cfg.moe_top_k)
         del logits, lse, counts
+    if model.cfg.moe_dropless:
+        dxe = _moe_experts_bwd_dropless(rt, unit, dye, ws, s, saved)
+        F_.moe_router_wgrad(dlogits, h2, s[4][0], s[4][1], dense=dense)
+        return F_.moe_dispatch_bwd(dxe, slot, dlogits, ws[4])
     dxe = torch.empty_like(xe)
     for e in range(E):
         rows = slice(e * C, (e + 1) * C)
@@ -337,6 +345,64 @@ def _moe_bwd(model, unit, dm, h2, ws, s, saved, daux=None):
         dxe[rows].copy_(F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, ju, wgu)))
     F_.moe_router_wgrad(dlogits, h2, s[4][0], s[4][1], dense=dense)
     return F_.moe_dispatch_bwd(dxe, slot, dlogits, ws[4])
+
+
+def _moe_fwd_dropless(model, i, h2, ws):
+    """:func:`_moe_fwd` with ``cfg.moe_dropless``: the same router, gates, tie rule, row-major order and combine, but
+    no capacity.  The assignments of expert e fill the segment [offsets[e], offsets[e + 1]) of one packed row space of
+    R = ``ref.moe_dropless_rows`` rows (128-aligned segments, static R), ``xe`` is [R, d], and the experts run as
+    two grouped GEMMs (gate|up on [R, 2f], down written straight into ``ye``) that read ``offsets`` on the device, so
+    a captured step replays with any routing.  Padding and tail rows are zero in ``xe`` and stay zero through SwiGLU.
+    The backward's tuple has ``gu`` / ``hh`` as single [R, .] tensors and ``offsets`` in place of C."""
+    cfg = model.cfg
+    E, K = cfg.n_experts, cfg.moe_top_k
+    expert, gate, logits = F_.moe_route(h2, ws[0], K)
+    extra = ()
+    if cfg.moe_aux_on:          # the layer keeps its own counts for the backward: see _moe_fwd
+        slot, src, _, counts, offsets = F_.moe_assign_dropless(expert, E)
+        model.moe_counts(h2.device)[i].copy_(counts)
+        lse, aux = F_.moe_aux_fwd(logits, counts, K, model.moe_aux(h2.device)[i])
+        extra = (logits, lse, counts)
+    else:
+        slot, src, _, _, offsets = F_.moe_assign_dropless(expert, E, model.moe_counts(h2.device)[i])
+    del logits
+    xe = F_.moe_dispatch(h2, src)
+    gu = F_.gemm_grouped_nt(xe, offsets, [ws[1 + 2 * e] for e in range(E)])
+    hh = F_.swiglu_fwd(gu)
+    ye = F_.gemm_grouped_nt(hh, offsets, [ws[2 + 2 * e] for e in range(E)])
+    m = F_.moe_combine(ye, slot, gate)
+    saved = (expert, gate, slot, src, xe, ye, gu, hh, offsets) + extra
+    return (m, saved, aux) if extra else (m, saved)
+
+
+def _moe_weights_t(rt, unit, ws, js):
+    """W^T of the parameters ``js`` of ``unit`` for a grouped data-gradient product: the engine's cached transposes
+    where it keeps them (``rt.weight_t``), else copies made here with ``transpose_into`` into one scratch tensor
+    [len(js), in, out] that lives until the product has run (engines whose parameters do not stay resident)."""
+    wts = [rt.weight_t(unit, j, ws[j]) for j in js]
+    if all(t is not None for t in wts):
+        return wts
+    w0 = ws[js[0]]
+    buf = torch.empty(len(js), w0.shape[1], w0.shape[0], dtype=w0.dtype, device=w0.device)
+    for t, j in zip(buf, js):
+        F_.transpose_into(ws[j], t)
+    return list(buf)
+
+
+def _moe_experts_bwd_dropless(rt, unit, dye, ws, s, saved):
+    """The experts' part of :func:`_moe_bwd` on the packed layout: two grouped TN products write every expert's two
+    weight gradients into their slots (an expert without rows gets exact zeros, or keeps its slot when accumulating)
+    and two grouped NT products on W^T give the data gradients -- four launches instead of 4 E GEMM calls and 2 E
+    slab copies.  Returns dxe [R, d] (zero in the padding and tail rows)."""
+    xe, gu, hh, offsets = saved[4], saved[6], saved[7], saved[8]
+    E = (len(ws) - 5) // 2
+    ju, jd = [5 + 2 * e for e in range(E)], [6 + 2 * e for e in range(E)]
+    F_.gemm_grouped_tn(dye, hh, offsets, [s[j][0] for j in jd], [s[j][1] for j in jd])
+    dhh = F_.gemm_grouped_nt(dye, offsets, _moe_weights_t(rt, unit, ws, jd))
+    dgu = F_.swiglu_bwd(dhh, gu)
+    del dhh
+    F_.gemm_grouped_tn(dgu, xe, offsets, [s[j][0] for j in ju], [s[j][1] for j in ju])
+    return F_.gemm_grouped_nt(dgu, offsets, _moe_weights_t(rt, unit, ws, ju))
 
 
 RECOMPUTE_MODES = ("off", "selective", "full")
@@ -623,6 +689,8 @@ class MistralLM(nn.Module):
                         "the total: lm_loss + aux_loss_coef * sum(balance_loss) + z_loss_coef * sum(z_loss)",
                "aux_loss_coef": cfg.moe_aux_loss_coef, "z_loss_coef": cfg.moe_z_loss_coef,
                "balance_loss": None, "z_loss": None}
+        if cfg.moe_dropless:        # no capacity: R packed slot rows per micro-step, nothing dropped
+            out.update(dropless=True, rows=ref.moe_dropless_rows(rows, E, K), capacity=None, drop_fraction=0.0)
         if self._moe_counts is not None:
             aux_on = cfg.moe_aux_on and self._moe_aux is not None
             # one device-to-host copy: the counts and, as fp32 bit patterns beside them, the two losses
@@ -631,7 +699,8 @@ class MistralLM(nn.Module):
             counts = both[:, :E]
             out["counts"] = counts.tolist()
             total = int(counts.sum())
-            out["drop_fraction"] = float((counts - C).clamp(min=0).sum()) / total if total else 0.0
+            if not cfg.moe_dropless:
+                out["drop_fraction"] = float((counts - C).clamp(min=0).sum()) / total if total else 0.0
             if aux_on:
                 aux = both[:, E:].contiguous().view(torch.float32)
                 out["balance_loss"], out["z_loss"] = aux[:, 0].tolist(), aux[:, 1].tolist()

@@ -78,7 +78,8 @@ def _moe_ffn(mlp, h, cfg):
     from ..ops import ref
     N = h.shape[0]
     E, K = cfg.n_experts, cfg.moe_top_k
-    C = ref.moe_capacity(N, E, K, cfg.moe_capacity_factor)
+    # dropless: a capacity of all N rows per expert, which no expert can exceed (a token chooses an expert once)
+    C = -(-N // 16) * 16 if cfg.moe_dropless else ref.moe_capacity(N, E, K, cfg.moe_capacity_factor)
     vals, idx = torch.sort(mlp.router(h), dim=-1, descending=True, stable=True)
     gate = torch.softmax(vals[:, :K], -1)
     slot, src, _, _ = ref.moe_assign(idx[:, :K].to(torch.int32), E, C)

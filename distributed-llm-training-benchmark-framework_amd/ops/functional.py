@@ -384,6 +384,45 @@ def moe_assign(expert, E, C, counts_out=None):
     return slot, src, src_k, _into(counts_out, counts)
 
 
+def moe_assign_dropless(expert, E, counts_out=None):
+    """(slot [N, K], src [R], src_k [R], counts [E], offsets [E + 1]), all int32: the packed dropless layout of
+    :func:`ref.moe_assign_dropless`, R = ``ref.moe_dropless_rows(N, E, K)``.  Three launches, no atomics, no host
+    read.  ``counts_out``: as in :func:`moe_assign`."""
+    if _gpu(expert):
+        slot, src, src_k, counts, offsets = ext().moe_assign_dropless(expert, E, counts_out)
+        return slot, src, src_k, counts, offsets
+    slot, src, src_k, counts, offsets = ref.moe_assign_dropless(expert, E)
+    return slot, src, src_k, _into(counts_out, counts), offsets
+
+
+def gemm_grouped_nt(a, offsets, bs, out=None):
+    """c[r] = a[r] bs[e]^T for the rows of segment e of ``offsets`` (int32 [E + 1] on the device, 128-aligned),
+    zeros past offsets[E]: one launch of the grouped MFMA GEMM (csrc/gemm_grouped.hip), which reads the offsets on
+    the device.  a [R, K] with R % 128 == 0 and K % 64 == 0, every b [N, K] with N % 128 == 0; bf16 or fp16.  There
+    is no other GPU path: a shape the kernel refuses is an error."""
+    if _gpu(a):
+        return ext().gemm_grouped_nt(a, offsets, list(bs), out)
+    return ref.gemm_grouped_nt(a, offsets, bs, out)
+
+
+def gemm_grouped_tn(dy, x, offsets, dws, accumulate):
+    """dws[e] (+)= dy[segment e]^T x[segment e], one launch, a fixed summation order (bitwise repeatable); an empty
+    segment writes zeros, or nothing where ``accumulate[e]``.  dy [R, M], x [R, N], every dw contiguous [M, N]; R, M
+    and N multiples of 128."""
+    if _gpu(dy):
+        ext().gemm_grouped_tn(dy, x, offsets, list(dws), [bool(a) for a in accumulate])
+    else:
+        ref.gemm_grouped_tn(dy, x, offsets, dws, accumulate)
+
+
+def transpose_into(src, dst):
+    """dst [C, R] = src [R, C]^T, both contiguous (the LDS-tiled transpose kernel on the GPU)."""
+    if _gpu(src):
+        ext().transpose_into(src, dst)
+    else:
+        dst.copy_(src.t())
+
+
 def moe_dispatch(h, src):
     return ext().moe_dispatch(h, src) if _gpu(h) else ref.moe_dispatch(h, src)
 

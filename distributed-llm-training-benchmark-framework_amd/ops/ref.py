@@ -424,6 +424,63 @@ def moe_assign(expert, E, C):
     return slot.to(torch.int32).view(N, K), src, src_k, onehot.sum(0).to(torch.int32)
 
 
+# Dropless routing: one packed row space [0, R) instead of E slabs of C rows.  Expert e owns the segment
+# [offsets[e], offsets[e + 1]), offsets = the exclusive prefix sum of the counts rounded up to MOE_SEGMENT rows (the
+# grouped GEMMs' tile, csrc/gemm_grouped.hip), and R is static: every assignment fits whatever the routing.
+MOE_SEGMENT = 128
+
+
+def moe_dropless_rows(N, E, K):
+    """R = roundup(N K, 128) + 128 E: at least sum_e roundup(counts[e], 128) for any counts that sum to N K."""
+    return -(-(N * K) // MOE_SEGMENT) * MOE_SEGMENT + MOE_SEGMENT * E
+
+
+def moe_assign_dropless(expert, E):
+    """(slot [N, K], src [R], src_k [R], counts [E], offsets [E + 1]), all int32.  Assignment (n, k) to expert e at
+    position p (the row-major order of :func:`moe_assign`) gets slot offsets[e] + p; nothing is dropped.  Every row
+    of [0, R) without an assignment -- the padding of a segment, the tail past offsets[E] -- has src = src_k = -1."""
+    N, K = expert.shape
+    R = moe_dropless_rows(N, E, K)
+    flat = expert.reshape(-1).long()
+    onehot = F.one_hot(flat, E)
+    pos = (onehot.cumsum(0) - onehot).gather(1, flat[:, None]).squeeze(1)
+    counts = onehot.sum(0)
+    seg = -(-counts // MOE_SEGMENT) * MOE_SEGMENT
+    offsets = torch.cat([torch.zeros(1, dtype=seg.dtype, device=seg.device), seg.cumsum(0)])
+    slot = offsets[flat] + pos
+    src = torch.full((R,), -1, dtype=torch.int32, device=expert.device)
+    src_k = torch.full((R,), -1, dtype=torch.int32, device=expert.device)
+    i = torch.arange(N * K, device=expert.device)
+    src[slot] = (i // K).to(torch.int32)
+    src_k[slot] = (i % K).to(torch.int32)
+    return slot.to(torch.int32).view(N, K), src, src_k, counts.to(torch.int32), offsets.to(torch.int32)
+
+
+def gemm_grouped_nt(a, offsets, bs, out=None):
+    """c[r] = a[r] bs[e]^T for the rows r of segment e = [offsets[e], offsets[e + 1]); rows past offsets[E] are zero.
+    A loop over the experts on the host-read offsets (the CPU definition of csrc/gemm_grouped.hip's NT kernel)."""
+    off = offsets.tolist()
+    c = torch.zeros(a.shape[0], bs[0].shape[0], dtype=a.dtype, device=a.device) if out is None else out.zero_()
+    for e, b in enumerate(bs):
+        if off[e + 1] > off[e]:
+            c[off[e]:off[e + 1]] = (_f(a[off[e]:off[e + 1]]) @ _f(b).t()).to(a.dtype)
+    return c
+
+
+def gemm_grouped_tn(dy, x, offsets, dws, accumulate):
+    """dws[e] (+)= dy[segment e]^T x[segment e] in place; an empty segment writes zeros, or nothing when
+    ``accumulate[e]``."""
+    off = offsets.tolist()
+    for e, dw in enumerate(dws):
+        rows = slice(off[e], off[e + 1])
+        v = _f(dy[rows]).t() @ _f(x[rows])
+        if accumulate[e]:
+            if off[e + 1] == off[e]:
+                continue
+            v = v + _f(dw)
+        dw.copy_(v)
+
+
 def _moe_rows(t, index):
     """t[index] with zero rows where index < 0."""
     ok = (index >= 0)[:, None]

@@ -3,6 +3,7 @@
 
     python scripts/bench_moe.py [--out profiles/moe_layer.txt] [--rows 4096,16384] [--factors 1.0,1.25,2.0] [--reps 9]
     python scripts/bench_moe.py --aux-loss-coef 0.01 --z-loss-coef 0.001      (appends to the same file)
+    python scripts/bench_moe.py --dropless                                    (appends to the same file)
 
 Times the FFN part of one MoE layer at the M7B shape (d 4096, f 14336, E 8, K 2), forward plus backward: route,
 assign, dispatch, the E experts, combine and their backward (``models/mistral.py::_moe_fwd`` / ``_moe_bwd``).  The
@@ -19,6 +20,12 @@ coefficients set against both at 0, interleaved rep by rep, and the router's wei
 zeros through the sparse kernel (the default) and the dense one (``dense=True``, what the layer runs with a loss on):
 batches of calls per event pair, the two kernels interleaved, once with the rows hot in the caches and once walking
 a ring of copies larger than the caches.
+
+With ``--dropless`` the script measures the dropless layer (``moe_dropless``: packed rows, grouped GEMMs) instead and
+appends to the file: the same layer (same weights, same rows) forward plus backward in dropless mode against (a) the
+capacity path at factor E / K, the only way to run it without drops, (b) the capacity path at factor 1.25 and (c) the
+dense FFN of equal nominal FLOPs, all interleaved rep by rep; and the two grouped kernels alone against E per-expert
+calls of the dense path's products at equal total rows (K rows / E per expert).
 """
 import argparse
 import os
@@ -51,6 +58,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--aux-loss-coef", type=float, default=0.0, help="load-balancing loss coefficient (0: off)")
     ap.add_argument("--z-loss-coef", type=float, default=0.0, help="router z-loss coefficient (0: off)")
+    ap.add_argument("--dropless", action="store_true", help="measure the dropless layer and the grouped kernels")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_moe.py measures on the GPU; none found")
@@ -83,6 +91,8 @@ def main():
 
     if a.aux_loss_coef or a.z_loss_coef:
         return aux_section(a, layer, F_, mistral, d, f, E, K, dev, dt)
+    if a.dropless:
+        return dropless_section(a, layer, F_, mistral, ref, d, f, E, K, dev, dt)
     dense = layer(None, K * f, 1.0)
     du = dense.unit_blocks[0]
     dws = dense.rt.acquire(du)
@@ -157,6 +167,90 @@ def main():
     with open(a.out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     print(f"wrote {a.out}")
+
+
+def dropless_section(a, layer, F_, mistral, ref, d, f, E, K, dev, dt):
+    """The dropless layer against the capacity path at factors E / K and 1.25 and the dense FFN, and the grouped
+    kernels against per-expert calls; appended to ``a.out``."""
+    name = torch.cuda.get_device_name(0)
+    lines = [f"# scripts/bench_moe.py --dropless on {name}, torch {torch.__version__}",
+             f"# one layer's FFN part, forward + backward, bf16, d {d}, f {f}, E {E}, K {K}: the same weights and rows in "
+             f"dropless mode (grouped GEMMs), on the capacity path at factor E/K = {E / K:g} (a: no drops) and 1.25 (b), "
+             f"and the dense FFN of hidden {K * f} (c)",
+             f"# medians of {a.reps} interleaved reps after 3 warm-up reps; ms; slot rows: R dropless, E C capacity",
+             "rows R dropless_ms EC_a cap_a_ms EC_b cap_b_ms dense_ms dropless/a dropless/b dropless/c"]
+    kern = ["# the grouped kernels alone against E per-expert calls at equal total rows (K rows / E rows per expert, "
+            "balanced); ms, medians; nt: [rows_e, d] x [2f, d]^T (gate|up forward), tn: dW [2f, d] = dy^T x",
+            "rows total_rows grouped_nt_ms per_expert_nt_ms nt_ratio grouped_tn_ms per_expert_tn_ms tn_ratio"]
+    dense = layer(None, K * f, 1.0)
+    dws = dense.rt.acquire(dense.unit_blocks[0])
+    ds = [(torch.empty_like(w), False) for w in dws]
+    moe = layer(E, f, 1.25)
+    mu = moe.unit_blocks[0]
+    mws = moe.rt.acquire(mu)
+    ms = [(torch.empty_like(w), False) for w in mws]
+    for rows in [int(r) for r in a.rows.split(",")]:
+        h = torch.randn(rows, d, device=dev).to(dt)
+        dm = torch.randn(rows, d, device=dev).to(dt)
+
+        def dense_step():
+            gu = F_.linear_fwd(h, dws[4])
+            hh = F_.swiglu_fwd(gu)
+            F_.linear_fwd(hh, dws[5])
+            F_.linear_wgrad(dm, hh, ds[5][0], None, False)
+            dgu = F_.swiglu_bwd(F_.linear_dgrad(dm, dws[5]), gu)
+            F_.linear_wgrad(dgu, h, ds[4][0], None, False)
+            return F_.linear_dgrad(dgu, dws[4])
+
+        def moe_step(dropless, factor):
+            moe.cfg.moe_dropless, moe.cfg.moe_capacity_factor = dropless, factor
+            _, saved = mistral._moe_fwd(moe, 0, h, mws[4:])
+            return mistral._moe_bwd(moe, mu, dm, h, mws, ms, saved)
+
+        steps = [lambda: moe_step(True, 1.25), lambda: moe_step(False, E / K), lambda: moe_step(False, 1.25), dense_step]
+        ts = [[] for _ in steps]
+        for rep_ in range(a.reps + 3):
+            for t, st in zip(ts, steps):
+                v = _timed(st)[0]
+                if rep_ >= 3:
+                    t.append(v)
+        md, ma, mb, mc = (statistics.median(t) for t in ts)
+        R = ref.moe_dropless_rows(rows, E, K)
+        ca, cb = ref.moe_capacity(rows, E, K, E / K), ref.moe_capacity(rows, E, K, 1.25)
+        lines.append(f"{rows} {R} {md:.3f} {E * ca} {ma:.3f} {E * cb} {mb:.3f} {mc:.3f} {md / ma:.3f} {md / mb:.3f} "
+                     f"{md / mc:.3f}")
+        print(lines[-1], flush=True)
+        torch.cuda.empty_cache()
+        # kernels alone: balanced segments of K rows / E rows, no tail
+        per = rows * K // E
+        tot = per * E
+        offsets = torch.arange(E + 1, device=dev, dtype=torch.int32) * per
+        xa = torch.randn(tot, d, device=dev).to(dt)
+        dy = torch.randn(tot, 2 * f, device=dev).to(dt)
+        wgu = [mws[5 + 2 * e] for e in range(E)]
+        dwg = [ms[5 + 2 * e][0] for e in range(E)]
+        out = torch.empty(tot, 2 * f, device=dev, dtype=dt)
+        calls = [lambda: F_.gemm_grouped_nt(xa, offsets, wgu, out),
+                 lambda: [F_.linear_fwd(xa[e * per:(e + 1) * per], wgu[e]) for e in range(E)],
+                 lambda: F_.gemm_grouped_tn(dy, xa, offsets, dwg, [False] * E),
+                 lambda: [F_.linear_wgrad(dy[e * per:(e + 1) * per], xa[e * per:(e + 1) * per], dwg[e], None, False)
+                          for e in range(E)]]
+        tk = [[] for _ in calls]
+        for rep_ in range(a.reps + 3):
+            for t, c in zip(tk, calls):
+                v = _timed(c)[0]
+                if rep_ >= 3:
+                    t.append(v)
+        gn, pn, gt, pt = (statistics.median(t) for t in tk)
+        kern.append(f"{rows} {tot} {gn:.3f} {pn:.3f} {gn / pn:.3f} {gt:.3f} {pt:.3f} {gt / pt:.3f}")
+        print(kern[-1], flush=True)
+        del xa, dy, out
+        torch.cuda.empty_cache()
+    lines += kern + [f"# written {time.strftime('%Y-%m-%d')}"]
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print(f"appended to {a.out}")
 
 
 WG_BATCH = 20        # router weight-gradient calls per event pair (one call is tens of microseconds)

@@ -108,6 +108,7 @@ def run_case(name, spec, world, rank, device, a):
         mcfg.n_experts, mcfg.moe_top_k = a.moe_experts, a.moe_top_k
         mcfg.moe_capacity_factor = a.moe_capacity_factor
         mcfg.moe_aux_loss_coef, mcfg.moe_z_loss_coef = a.moe_aux_loss_coef, a.moe_z_loss_coef
+        mcfg.moe_dropless = a.moe_dropless
     mcfg.validate()
     with torch.device(device):
         model = build_model(mcfg)
@@ -192,6 +193,7 @@ def main():
     ap.add_argument("--moe-capacity-factor", type=float, default=1.25)
     ap.add_argument("--moe-aux-loss-coef", type=float, default=0.0, help="with --moe-experts: load-balancing loss")
     ap.add_argument("--moe-z-loss-coef", type=float, default=0.0, help="with --moe-experts: router z-loss")
+    ap.add_argument("--moe-dropless", action="store_true", help="with --moe-experts: the dropless grouped-GEMM path")
     a = ap.parse_args()
     from dltb.utils.dist import cleanup_distributed, setup_distributed
     world = int(os.environ.get("WORLD_SIZE", "1"))
