@@ -59,6 +59,16 @@ void dltb_transpose(const void* src, void* dst, int R, int C, hipStream_t st);
 void dltb_transpose_batched(const void* src, void* dst, int R, int C, int nb, long sbs, long dbs,
                             hipStream_t st);
 
+// qknorm.hip: per-head RMSNorm over D (64 or 128) of the q and k heads fused with the rotate-half RoPE, in place on
+// rows of width `stride`; raw: contiguous [N, (Hq + Hkv) D] copy of the q|k columns as they were
+void dltb_qknorm_rope_fwd(void* qkv, void* raw, const void* wq, const void* wk, const float* cosb,
+                          const float* sinb, int N, int T, int Hq, int Hkv, int D, int stride, float eps,
+                          hipStream_t st);
+int dltb_qknorm_partials(int N);    // G: workgroups of the backward = rows of part_q / part_k ([G, D] fp32)
+void dltb_qknorm_rope_bwd(void* dqkv, const void* raw, const void* wq, const void* wk, const float* cosb,
+                          const float* sinb, float* part_q, float* part_k, int N, int T, int Hq, int Hkv, int D,
+                          int stride, float eps, hipStream_t st);
+
 // comm_emu.hip: one emulated RCCL collective (DLTB_COMM=emulate:N) -- `channels` paced workgroups
 // that read `traffic` (`passes` times) and write dst[r * rep_stride + j] = scale * src[j]
 void dltb_comm_emu(const void* traffic, long traffic_bytes, int passes, void* dst, const void* src, long n,

@@ -15,7 +15,7 @@ Differences that make the numbers honest (recorded in the extended sidecar):
 Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device, --bucket-mb, --dropout, --seed,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
 --doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk, --moe-experts, --moe-top-k,
---moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef, --moe-dropless.
+--moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef, --moe-dropless, --qk-norm.
 """
 import argparse
 import json
@@ -103,6 +103,10 @@ def build_parser():
                    help="with --moe-experts: no capacity, every assignment is kept; the experts' rows are packed into "
                         "128-aligned segments of roundup(rows * K, 128) + 128 * E slot rows and run as grouped GEMMs "
                         "(not together with --moe-capacity-factor); default: the fixed-capacity path")
+    p.add_argument("--qk-norm", action="store_true",
+                   help="causal tiers: RMSNorm over head_dim on every query and key head before RoPE, with one learned "
+                        "[head_dim] weight for q and one for k per layer (Qwen3 / OLMo-2 / Gemma-3 style), fused with "
+                        "RoPE into one pass; default: off")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -222,6 +226,17 @@ def check_head_chunk(n, mcfg, tier):
         raise ValueError(f"--head-chunk must be a positive multiple of 16, got {n}")
 
 
+def check_qk_norm(on, mcfg, tier):
+    """ValueError when ``--qk-norm`` is set for a tier without RoPE attention; sets it on ``mcfg``."""
+    if not on:
+        return
+    if not mcfg.causal:
+        raise ValueError(f"--qk-norm needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the reference's "
+                         "attention with learned positions and no RoPE")
+    mcfg.qk_norm = True
+    mcfg.validate()
+
+
 def check_moe(experts, top_k, factor, recompute, mcfg, tier, aux_coef=None, z_coef=None, dropless=False):
     """ValueError when the ``--moe-*`` flags are set for a tier without the routed FFN or together with
     ``--activation-recompute``, or ``--moe-dropless`` together with an explicit ``--moe-capacity-factor``; sets them
@@ -332,6 +347,7 @@ def train(args):
                   getattr(args, "moe_capacity_factor", None), recompute, mcfg, args.tier,
                   getattr(args, "moe_aux_loss_coef", None), getattr(args, "moe_z_loss_coef", None),
                   bool(getattr(args, "moe_dropless", False)))
+        check_qk_norm(bool(getattr(args, "qk_norm", False)), mcfg, args.tier)
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -361,6 +377,8 @@ def train(args):
                   f"expert for the {head_rows} rows per micro-step (factor {mcfg.moe_capacity_factor}), "
                   f"load-balancing loss coefficient {mcfg.moe_aux_loss_coef}, router z-loss coefficient "
                   f"{mcfg.moe_z_loss_coef}", flush=True)
+        if mcfg.qk_norm and is_main:
+            print(f"QK-norm: RMSNorm over head_dim {mcfg.head_dim} on q and k, fused with RoPE", flush=True)
         cp = None
         if cp_n > 1:
             cp = _context.ContextParallel(cp_n, cp_layout, mcfg.sliding_window, world, rank)
@@ -611,6 +629,10 @@ def main(argv=None):
         check_moe(args.moe_experts, args.moe_top_k, args.moe_capacity_factor, args.activation_recompute,
                   get_model_config(args.tier, args.seq_len), args.tier, args.moe_aux_loss_coef,
                   args.moe_z_loss_coef, args.moe_dropless)
+    except ValueError as e:
+        parser.error(str(e))
+    try:
+        check_qk_norm(args.qk_norm, get_model_config(args.tier, args.seq_len), args.tier)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

@@ -53,6 +53,9 @@ class ModelConfig:
     # one [R, d] buffer, R = roundup(rows * moe_top_k, 128) + 128 * n_experts, and run as grouped GEMMs that read the
     # segment bounds on the device (csrc/gemm_grouped.hip); moe_capacity_factor is not used.
     moe_dropless: bool = False
+    # QK-norm (mistral arch): an RMSNorm over head_dim on every query head and every key head before RoPE, with one
+    # learned [head_dim] weight for q and one for k per layer (eps = norm_eps); fused with RoPE (csrc/qknorm.hip)
+    qk_norm: bool = False
 
     def __post_init__(self):
         self.validate()
@@ -71,6 +74,13 @@ class ModelConfig:
                 raise ValueError(f"doc_eos_id must be an integer in [0, vocab_size) or None, got {e!r}")
             if not self.causal:
                 raise ValueError("doc_eos_id (document-masked attention) needs causal=True")
+        if not isinstance(self.qk_norm, bool):
+            raise ValueError(f"qk_norm must be a bool, got {self.qk_norm!r}")
+        if self.qk_norm:
+            if self.arch != "mistral":
+                raise ValueError(f"qk_norm (QK-norm fused with RoPE) needs the mistral arch, got arch {self.arch!r}")
+            if self.head_dim not in (64, 128):
+                raise ValueError(f"qk_norm needs head_dim 64 or 128, got {self.head_dim}")
         k, cf = self.moe_top_k, self.moe_capacity_factor
         if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4):
             raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
@@ -138,6 +148,8 @@ class ModelConfig:
         if self.n_experts:       # every expert's FFN plus the router
             ffn = self.n_experts * ffn + self.n_experts * d
         per_block = d + (d * d + 2 * kvd * d) + d * d + d + ffn
+        if self.qk_norm:         # the q and the k weight, [head_dim] each
+            per_block += 2 * hd
         head = 0 if self.tie_embeddings else V * d
         return V * d + L * per_block + d + head
 
@@ -147,7 +159,8 @@ class ModelConfig:
         ``visible_pairs_per_row``: the measured number of visible (query, key) pairs of a row of ``seq_len``
         tokens (a document mask depends on the data: ``SyntheticDataset.visible_pairs_per_row``); it replaces
         the T^2 / 2 (or window) count.  Without it the result is exactly the formula above.  With ``n_experts`` the
-        FFN term counts ``moe_top_k`` experts and the router product per token."""
+        FFN term counts ``moe_top_k`` experts and the router product per token.  ``qk_norm`` changes nothing here: it
+        adds no matrix product (its 2 * head_dim weights per layer are elementwise), like the other norms."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d

@@ -23,6 +23,11 @@ With ``cfg.moe_aux_loss_coef`` / ``cfg.moe_z_loss_coef`` every layer also return
 the loss is ``lm_loss + a sum_layers balance + b sum_layers z`` (ops/ref.py ``moe_aux_fwd``), on the rank's local rows.
 With ``cfg.moe_dropless`` there is no capacity: the experts' rows are packed into 128-aligned segments and run as
 grouped GEMMs that read the segment bounds on the device (``_moe_fwd_dropless``, csrc/gemm_grouped.hip).
+
+With ``cfg.qk_norm`` every query head and every key head goes through an RMSNorm over ``head_dim`` before RoPE, with
+one learned [head_dim] weight for q and one for k per layer: ``self_attn.{q_norm,k_norm}.weight``, the LAST two
+entries of the layer's parameter list.  Norm and RoPE are one in-place pass (``qknorm_rope_fwd`` / ``_bwd_``,
+csrc/qknorm.hip) where the flag-off path runs ``rope_``; the forward keeps ``raw``, the q|k columns before the norm.
 """
 import math
 
@@ -42,10 +47,13 @@ class _RMSNorm(nn.Module):
 
 
 class _Attn(nn.Module):
-    def __init__(self, d, kvd):
+    def __init__(self, d, kvd, qk_norm_dim=None):
         super().__init__()
         self.qkv_proj = nn.Linear(d, d + 2 * kvd, bias=False)
         self.o_proj = nn.Linear(d, d, bias=False)
+        if qk_norm_dim:         # QK-norm: one [head_dim] weight for the query heads, one for the key heads
+            self.q_norm = _RMSNorm(qk_norm_dim)
+            self.k_norm = _RMSNorm(qk_norm_dim)
 
 
 class _MLP(nn.Module):
@@ -69,11 +77,17 @@ class MistralLayer(nn.Module):
         super().__init__()
         d = cfg.n_embd
         self.input_layernorm = _RMSNorm(d)
-        self.self_attn = _Attn(d, cfg.kv_heads * cfg.head_dim)
+        self.self_attn = _Attn(d, cfg.kv_heads * cfg.head_dim, cfg.head_dim if cfg.qk_norm else None)
+        self.qk_norm = cfg.qk_norm
         self.post_attention_layernorm = _RMSNorm(d)
         self.mlp = _MoE(d, cfg.ffn_dim, cfg.n_experts) if cfg.n_experts else _MLP(d, cfg.ffn_dim)
 
     def param_list(self):
+        # the QK-norm weights come last, so the dense (4, 5) and MoE (4, 5 + 2e, 6 + 2e) indices hold with them
+        tail = []
+        if self.qk_norm:
+            tail = [("self_attn.q_norm.weight", self.self_attn.q_norm.weight),
+                    ("self_attn.k_norm.weight", self.self_attn.k_norm.weight)]
         head = [("input_layernorm.weight", self.input_layernorm.weight),
                 ("self_attn.qkv_proj.weight", self.self_attn.qkv_proj.weight),
                 ("self_attn.o_proj.weight", self.self_attn.o_proj.weight),
@@ -83,9 +97,9 @@ class MistralLayer(nn.Module):
             for e, ex in enumerate(self.mlp.experts):
                 moe += [(f"mlp.experts.{e}.gate_up_proj.weight", ex.gate_up_proj.weight),
                         (f"mlp.experts.{e}.down_proj.weight", ex.down_proj.weight)]
-            return head + moe
+            return head + moe + tail
         return head + [("mlp.gate_up_proj.weight", self.mlp.gate_up_proj.weight),
-                       ("mlp.down_proj.weight", self.mlp.down_proj.weight)]
+                       ("mlp.down_proj.weight", self.mlp.down_proj.weight)] + tail
 
 
 class _EmbedFn(torch.autograd.Function):
@@ -109,29 +123,66 @@ class _EmbedFn(torch.autograd.Function):
         return None, None, None
 
 
-def _cp_rope_gather(model, qkv, Hq, Hkv, D):
+def _n_block_weights(cfg, ws):
+    """How many of a layer's parameters ``ws`` come before the QK-norm pair (the norms, projections and the FFN)."""
+    return len(ws) - (2 if cfg.qk_norm else 0)
+
+
+def _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn):
+    """RoPE in place on the q|k columns of ``qkv`` (rows of T positions); with ``qkn`` = (wq, wk) the fused
+    QK-norm + RoPE pass instead.  Returns ``raw`` (None without QK-norm)."""
+    cos, sin = model.rope(qkv.device, T)
+    if qkn is None:
+        F_.rope_(qkv, cos, sin, T, Hq + Hkv, D, False)
+        return None
+    return F_.qknorm_rope_fwd(qkv, qkn[0], qkn[1], cos, sin, T, Hq, Hkv, D, model.cfg.norm_eps)
+
+
+def _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, sq, sk, red):
+    """The backward of :func:`_rope_fwd`, in place on the q|k columns of ``dqkv``: the inverse rotation (RoPE is
+    orthogonal: grad = R(-theta) g), with QK-norm the fused backward, whose weight-gradient partials go to the
+    gradient slots ``sq`` / ``sk`` ((tensor, accumulate) each) through ``red`` with the layer's norm partials."""
+    cos, sin = model.rope(dqkv.device, T)
+    if qkn is None:
+        F_.rope_(dqkv, cos, sin, T, Hq + Hkv, D, True)
+        return
+    pq, pk = F_.qknorm_rope_bwd_(dqkv, raw, qkn[0], qkn[1], cos, sin, T, Hq, Hkv, D, model.cfg.norm_eps)
+    F_.reduce_partials(red, pq, sq[0], sq[1])
+    F_.reduce_partials(red, pk, sk[0], sk[1])
+
+
+def _cp_rope_gather(model, qkv, Hq, Hkv, D, qkn=None):
     """The part of the context-parallel attention forward before its kernels: RoPE in place with each range's
-    positions, then the all-gather of K | V into position order.  Returns kv.  Also the backward's re-gather
-    under ``activation_recompute = "full"``, which does not keep kv."""
+    positions, then the all-gather of K | V into position order.  Returns (kv, raw).  Also the backward's
+    re-gather under ``activation_recompute = "full"``, which does not keep kv.  With ``qkn`` = (wq, wk) each range
+    runs the fused QK-norm + RoPE pass with its own cos / sin rows (the keys are normalised before the gather) and
+    ``raw`` is the ranges' q|k columns before it, range-major like ``qkv``; else ``raw`` is None."""
     cp = model.cp
     B, T = model._cur_full_bt
     n = qkv.shape[0] // len(cp.ranges(T))
     cos, sin = model.rope(qkv.device, T)
+    raws = []
     for j, (c, s_) in enumerate(cp.rope_rows(cos, sin, T)):
-        F_.rope_(qkv[j * n:(j + 1) * n], c, s_, n // B, Hq + Hkv, D, False)
-    return cp.gather_kv(qkv[:, Hq * D:], B, T)    # waits for the gather: the kernels read it
+        if qkn is None:
+            F_.rope_(qkv[j * n:(j + 1) * n], c, s_, n // B, Hq + Hkv, D, False)
+        else:
+            raws.append(F_.qknorm_rope_fwd(qkv[j * n:(j + 1) * n], qkn[0], qkn[1], c, s_, n // B, Hq, Hkv, D,
+                                           model.cfg.norm_eps))
+    # waits for the gather: the kernels read it
+    return cp.gather_kv(qkv[:, Hq * D:], B, T), (raws if raws else None)
 
 
-def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed):
+def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed, qkn=None):
     """Context-parallel attention forward (parallel/context.py): RoPE with each range's positions, all-gather of
     K | V into position order, then the range kernels -- the local queries of each range against all T keys.
-    ``qkv`` holds the local tokens range-major, so a range's rows are one block.  Returns (o, lse per range, kv)."""
+    ``qkv`` holds the local tokens range-major, so a range's rows are one block.  Returns (o, lse per range, kv,
+    raw); ``qkn`` / ``raw``: :func:`_cp_rope_gather`."""
     cp = model.cp
     B, T = model._cur_full_bt
     rngs = cp.ranges(T)
     n = qkv.shape[0] // len(rngs)
     qd, kd = Hq * D, Hkv * D
-    kv = _cp_rope_gather(model, qkv, Hq, Hkv, D)
+    kv, raw = _cp_rope_gather(model, qkv, Hq, Hkv, D, qkn)
     o = torch.empty(qkv.shape[0], qd, dtype=qkv.dtype, device=qkv.device)
     lses = []
     for j, rng in enumerate(rngs):
@@ -139,14 +190,17 @@ def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed):
                                 1.0 / math.sqrt(D), True, 0.0, seed, 0, o_out=o[j * n:(j + 1) * n],
                                 window=window, bounds=bounds, q_range=rng)
         lses.append(lse)
-    return o, lses, kv
+    return o, lses, kv, raw
 
 
-def _cp_attn_bwd(model, qkv, kv, o, do, lses, dqkv, Hq, Hkv, D, window, bounds, seed):
+def _cp_attn_bwd(model, qkv, kv, o, do, lses, dqkv, Hq, Hkv, D, window, bounds, seed, qkn=None, raw=None, sq=None,
+                 sk=None, red=None):
     """The backward of :func:`_cp_attn_fwd`: dQ of each range into its rows of ``dqkv``; each range's dK | dV
     over all T rows (zero where its queries see nothing), the zigzag pair summed by one add; reduce-scatter over
     the group into the local K | V columns of ``dqkv``; then the inverse RoPE of the local rows as without
-    context parallelism."""
+    context parallelism.  With ``qkn`` = (wq, wk) the fused QK-norm + RoPE backward runs per range instead (``raw``:
+    the forward's list); the ranges' weight-gradient partials fill one partial matrix per weight, so the later
+    ranges' sums accumulate onto the first's in the one fixed-order reduction into the slot ``sq`` / ``sk``."""
     cp = model.cp
     B, T = model._cur_full_bt
     rngs = cp.ranges(T)
@@ -162,8 +216,18 @@ def _cp_attn_bwd(model, qkv, kv, o, do, lses, dqkv, Hq, Hkv, D, window, bounds, 
         dkv = part if dkv is None else dkv.add_(part)
     cp.scatter_dkv(dkv, dqkv[:, qd:], B, T)       # waits for the reduce-scatter: the inverse RoPE reads it
     cos, sin = model.rope(qkv.device, T)
+    if qkn is not None:
+        G = F_.qknorm_partials(dqkv, n)
+        part = torch.empty(2, len(rngs) * G, D, dtype=torch.float32, device=dqkv.device)
     for j, (c, s_) in enumerate(cp.rope_rows(cos, sin, T)):
-        F_.rope_(dqkv[j * n:(j + 1) * n], c, s_, n // B, Hq + Hkv, D, True)
+        if qkn is None:
+            F_.rope_(dqkv[j * n:(j + 1) * n], c, s_, n // B, Hq + Hkv, D, True)
+        else:
+            F_.qknorm_rope_bwd_(dqkv[j * n:(j + 1) * n], raw[j], qkn[0], qkn[1], c, s_, n // B, Hq, Hkv, D,
+                                model.cfg.norm_eps, part_out=part, g_off=j * G)
+    if qkn is not None:
+        F_.reduce_partials(red, part[0], sq[0], sq[1])
+        F_.reduce_partials(red, part[1], sk[0], sk[1])
 
 
 class _LayerFn(torch.autograd.Function):
@@ -177,6 +241,8 @@ class _LayerFn(torch.autograd.Function):
                              f"(activation_recompute = {ctx.recompute!r}, n_experts = {cfg.n_experts})")
         ws = rt.acquire(unit)
         (w_in, wqkv, wo, w_post) = ws[:4]
+        nb = _n_block_weights(cfg, ws)
+        qkn = tuple(ws[nb:]) if cfg.qk_norm else None       # (q weight, k weight) of QK-norm
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
         _, h1, _, rstd1 = F_.norm_fwd(x, None, w_in, None, cfg.norm_eps, True)
@@ -186,10 +252,9 @@ class _LayerFn(torch.autograd.Function):
         bounds = model._cur_bounds
         window = 0 if bounds is not None else cfg.sliding_window or 0
         if model.cp is not None:      # context parallel: local queries against the group's gathered K | V
-            o, lse, aux = _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, rt.seed)
+            o, lse, aux, raw = _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, rt.seed, qkn)
         else:
-            cos, sin = model.rope(x.device, T)
-            F_.rope_(qkv, cos, sin, T, Hq + Hkv, D, False)
+            raw = _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn)
             o, lse, aux = F_.attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
                                       1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds)
         a = F_.linear_fwd(o, wo)
@@ -197,23 +262,24 @@ class _LayerFn(torch.autograd.Function):
         ctx.moe = None
         router_losses = None
         if cfg.n_experts:       # top-k routed experts instead of the dense FFN; gu / hh are per expert, in ctx.moe
-            m, ctx.moe, *rest = _moe_fwd(model, i, h2, ws[4:])
+            m, ctx.moe, *rest = _moe_fwd(model, i, h2, ws[4:nb])
             gu = hh = None
             if rest:            # the layer's (balance, z): a second, differentiable output (not kept on ctx)
                 router_losses = rest[0]
         else:
-            wgu, wd = ws[4:]
+            wgu, wd = ws[4:6]
             gu = F_.linear_fwd(h2, wgu)
             hh = F_.swiglu_fwd(gu)
             m = F_.linear_fwd(hh, wd)
         x2 = F_.dropout(x1, m, 0.0, rt.seed, 0)
         rt.release_forward(unit)
         ctx.model, ctx.i = model, i
-        ctx.saved = (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh)
+        # raw: the q|k columns before QK-norm (None without it)
+        ctx.saved = (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh, raw)
         if ctx.recompute == "selective":      # the backward rebuilds h1, h2 (norm_apply) and hh (swiglu_bwd_h)
-            ctx.saved = (x, None, rstd1, qkv, o, lse, aux, x1, None, rstd2, gu, None)
+            ctx.saved = (x, None, rstd1, qkv, o, lse, aux, x1, None, rstd2, gu, None, raw)
         elif ctx.recompute == "full":         # ... and everything else but the attention output
-            ctx.saved = (x, None, None, None, o, lse, None, None, None, None, None, None)
+            ctx.saved = (x, None, None, None, o, lse, None, None, None, None, None, None, None)
         ctx.bounds = bounds
         return x2 if router_losses is None else (x2, router_losses)
 
@@ -223,20 +289,22 @@ class _LayerFn(torch.autograd.Function):
             return _layer_backward_recompute(ctx, dx2), None, None
         model, i = ctx.model, ctx.i
         rt, unit = model.rt, model.unit_blocks[i]
-        (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh) = ctx.saved
+        (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh, raw) = ctx.saved
         ctx.saved = None
         ws = rt.acquire_backward(unit)
         (w_in, wqkv, wo, w_post) = ws[:4]
         cfg = model.cfg
+        nb = _n_block_weights(cfg, ws)
+        qkn = tuple(ws[nb:]) if cfg.qk_norm else None
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
         dx2 = dx2.contiguous()
         s = [rt.grad_slot(unit, j) for j in range(len(ws))]
         if ctx.moe is not None:
-            dh2 = _moe_bwd(model, unit, dx2, h2, ws, s, ctx.moe, daux)
+            dh2 = _moe_bwd(model, unit, dx2, h2, ws[:nb], s[:nb], ctx.moe, daux)
             ctx.moe = None
         else:
-            wgu, wd = ws[4:]
+            wgu, wd = ws[4:6]
             F_.linear_wgrad(dx2, hh, s[5][0], None, s[5][1])
             dhh = F_.linear_dgrad(dx2, wd, rt.weight_t(unit, 5, wd))
             dgu = F_.swiglu_bwd(dhh, gu)
@@ -251,13 +319,13 @@ class _LayerFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         window = 0 if ctx.bounds is not None else cfg.sliding_window or 0
         if model.cp is not None:      # aux: the gathered K | V of the forward
-            _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed)
+            _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed, qkn, raw,
+                         s[nb] if qkn else None, s[nb + 1] if qkn else None, red)
         else:
-            cos, sin = model.rope(dx2.device, T)
             F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                         dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
                         1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds)
-            F_.rope_(dqkv, cos, sin, T, Hq + Hkv, D, True)      # RoPE is orthogonal: grad = R(-theta) g
+            _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, s[nb] if qkn else None, s[nb + 1] if qkn else None, red)
         ctx.bounds = None
         F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
         dh1 = F_.linear_dgrad(dqkv, wqkv, rt.weight_t(unit, 1, wqkv))
@@ -419,6 +487,7 @@ def _layer_backward_recompute(ctx, dx2):
 
     * ``selective`` kept everything but the norm outputs h1, h2 and the SwiGLU output hh; they come back from
       elementwise kernels (``norm_apply`` from the kept row statistics, ``swiglu_bwd_h`` inside the SwiGLU backward).
+    * with QK-norm both modes treat ``raw`` like qkv: ``selective`` keeps it, ``full`` rebuilds it with qkv.
     * ``full`` kept x, o, lse.  The MLP half (a = o Wo^T, x1 / h2 / rstd2, gu) is rebuilt first and the attention
       half (h1 / rstd1, qkv + RoPE, under context parallelism the gathered K | V) only when the MLP half has been
       consumed and freed, so the rebuilt working set is half a layer's.  Attention itself and the down projection
@@ -430,15 +499,18 @@ def _layer_backward_recompute(ctx, dx2):
     model, i = ctx.model, ctx.i
     full = ctx.recompute == "full"
     rt, unit = model.rt, model.unit_blocks[i]
-    (x, _, rstd1, qkv, o, lse, aux, x1, _, rstd2, gu, _) = ctx.saved
+    (x, _, rstd1, qkv, o, lse, aux, x1, _, rstd2, gu, _, raw) = ctx.saved
     ctx.saved = None
-    (w_in, wqkv, wo, w_post, wgu, wd) = rt.acquire_backward(unit)
+    ws = rt.acquire_backward(unit)
+    (w_in, wqkv, wo, w_post, wgu, wd) = ws[:6]
     cfg = model.cfg
+    qkn = tuple(ws[6:]) if cfg.qk_norm else None            # the dense layer's QK-norm pair: parameters 6, 7
     B, T = model._cur_bt
     Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
     qd, kd = Hq * D, Hkv * D
     dx2 = dx2.contiguous()
-    s = [rt.grad_slot(unit, j) for j in range(6)]
+    s = [rt.grad_slot(unit, j) for j in range(len(ws))]
+    sq, sk = (s[6], s[7]) if qkn else (None, None)
     # ---- MLP half
     if full:
         a = F_.linear_fwd(o, wo)
@@ -468,23 +540,21 @@ def _layer_backward_recompute(ctx, dx2):
         _, h1, _, rstd1 = F_.norm_fwd(x, None, w_in, None, cfg.norm_eps, True)
         qkv = F_.linear_fwd(h1, wqkv)
         if model.cp is not None:      # the re-gather: one more all-gather per layer, in layer order on every rank
-            aux = _cp_rope_gather(model, qkv, Hq, Hkv, D)
+            aux, raw = _cp_rope_gather(model, qkv, Hq, Hkv, D, qkn)
         else:
-            cos, sin = model.rope(x.device, T)
-            F_.rope_(qkv, cos, sin, T, Hq + Hkv, D, False)
+            raw = _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn)
     else:
         h1 = F_.norm_apply(x, w_in, None, None, rstd1, True)
     dqkv = torch.empty_like(qkv)
     if model.cp is not None:
-        _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed)
+        _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed, qkn, raw, sq, sk, red)
     else:
-        cos, sin = model.rope(x.device, T)
         F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                     dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
                     1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds)
-        F_.rope_(dqkv, cos, sin, T, Hq + Hkv, D, True)
+        _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, sq, sk, red)
     ctx.bounds = None
-    del qkv, aux, o, do, lse
+    del qkv, aux, o, do, lse, raw
     F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
     del h1
     dh1 = F_.linear_dgrad(dqkv, wqkv, rt.weight_t(unit, 1, wqkv))
@@ -636,7 +706,8 @@ class MistralLM(nn.Module):
         self._rope = {}
         self.cp = None          # parallel.context.ContextParallel.attach(): a layout, not a model property
         # which of a layer's activations its forward keeps for the backward (set by the harness, like cp):
-        # "off" all twelve, "selective" without h1 / h2 / hh, "full" only x, o, lse (_layer_backward_recompute)
+        # "off" all twelve (thirteen with QK-norm's raw), "selective" without h1 / h2 / hh, "full" only x, o, lse
+        # (_layer_backward_recompute)
         self.activation_recompute = "off"
         # rows per chunk of the LM head (set by the harness too): None materialises the [rows, V] logits and keeps
         # them as dlogits for the backward; N keeps their log-sum-exp rows and re-runs the product per chunk

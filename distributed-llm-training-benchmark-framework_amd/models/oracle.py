@@ -129,6 +129,9 @@ class OracleMistral(nn.Module):
             layer.self_attn = nn.Module()
             layer.self_attn.qkv_proj = nn.Linear(d, d + 2 * kvd, bias=False)
             layer.self_attn.o_proj = nn.Linear(d, d, bias=False)
+            if cfg.qk_norm:         # RMSNorm over head_dim of every q / k head before RoPE
+                layer.self_attn.q_norm = _RMSNorm(hd, cfg.norm_eps)
+                layer.self_attn.k_norm = _RMSNorm(hd, cfg.norm_eps)
             layer.post_attention_layernorm = _RMSNorm(d, cfg.norm_eps)
             layer.mlp = nn.Module()
             if cfg.n_experts:       # mixture of experts: a router and n_experts FFNs (autograd only, _moe_ffn)
@@ -162,6 +165,8 @@ class OracleMistral(nn.Module):
             q = qkv[..., :H * hd].view(B, T, H, hd).transpose(1, 2)
             k = qkv[..., H * hd:(H + Hkv) * hd].view(B, T, Hkv, hd).transpose(1, 2)
             v = qkv[..., (H + Hkv) * hd:].view(B, T, Hkv, hd).transpose(1, 2)
+            if cfg.qk_norm:
+                q, k = layer.self_attn.q_norm(q), layer.self_attn.k_norm(k)
             q, k = _rope(q, cos, sin), _rope(k, cos, sin)
             k = k.repeat_interleave(H // Hkv, 1)
             v = v.repeat_interleave(H // Hkv, 1)

@@ -485,6 +485,46 @@ def rope_(qkv2d, cos, sin, T, heads, D, inverse=False):
         ref.rope_(qkv2d, cos, sin, T, heads, D, inverse)
 
 
+def qknorm_rope_fwd(qkv2d, wq, wk, cos, sin, T, Hq, Hkv, D, eps):
+    """QK-norm fused with RoPE, in place on the q|k columns of ``qkv2d`` (rows may be strided): RMSNorm over D of
+    every q head (weight ``wq``) and k head (``wk``), then :func:`rope_`'s rotation, one rounding (csrc/qknorm.hip).
+    Returns ``raw``: a contiguous [N, (Hq + Hkv) D] copy of the q|k columns as they were, for the backward."""
+    if _gpu(qkv2d):
+        return ext().qknorm_rope_fwd(qkv2d, wq, wk, cos, sin, T, Hq, Hkv, D, eps)
+    return ref.qknorm_rope_fwd(qkv2d, wq, wk, cos, sin, T, Hq, Hkv, D, eps)
+
+
+def qknorm_partials(like, N):
+    """Rows of one call's weight-gradient partials for N token rows on ``like``'s device (a function of N only)."""
+    return ext().qknorm_partials(N) if _gpu(like) else 1
+
+
+def qknorm_rope_bwd_(dqkv2d, raw, wq, wk, cos, sin, T, Hq, Hkv, D, eps, part_out=None, g_off=0):
+    """The backward of :func:`qknorm_rope_fwd`, in place on the q|k columns of ``dqkv2d``.  Returns the fp32
+    weight-gradient partials (dwq_part, dwk_part), [G, D] each with G = :func:`qknorm_partials` (N); they reach
+    their gradient slots through :func:`reduce_partials`.  ``part_out`` (fp32 [2, Gtot, D]) and ``g_off``: write
+    them at row ``g_off`` of a larger partial matrix, so that several calls' sums meet in one slot by one reduction
+    (two segments of one ``colreduce_multi`` launch must not share a slot)."""
+    if _gpu(dqkv2d):
+        part = ext().qknorm_rope_bwd_(dqkv2d, raw, wq, wk, cos, sin, T, Hq, Hkv, D, eps, part_out, g_off)
+        G = ext().qknorm_partials(dqkv2d.shape[0])
+        return part[0, g_off:g_off + G], part[1, g_off:g_off + G]
+    pq, pk = ref.qknorm_rope_bwd_(dqkv2d, raw, wq, wk, cos, sin, T, Hq, Hkv, D, eps)
+    if part_out is not None:
+        part_out[0, g_off:g_off + 1].copy_(pq)
+        part_out[1, g_off:g_off + 1].copy_(pk)
+    return pq, pk
+
+
+def reduce_partials(red, part2d, out, accumulate):
+    """Sum the fp32 column partials ``part2d`` [P, k] into the gradient slot ``out``: on the GPU at ``red.flush()``
+    (with the unit's norm partials), on the CPU at once."""
+    if _gpu(part2d):
+        red.add(part2d, out, accumulate)
+    else:
+        ref._write_slot(out, part2d.sum(0), accumulate)
+
+
 # ------------------------------------------------------------------------------ embedding / loss
 def embed_fwd(idx, wte, wpe, p, seed, site):
     if _gpu(wte):

@@ -165,6 +165,53 @@ def rope_(qkv2d, cos, sin, T, heads, D, inverse=False):
     qkv2d[:, :heads * D] = torch.cat([o1, o2], -1).reshape(N, heads * D).to(qkv2d.dtype)
 
 
+def _qk_weight(wq, wk, Hq, Hkv, D):
+    """[Hq + Hkv, D]: the q weight for the q heads, the k weight for the k heads."""
+    return torch.cat([_f(wq).reshape(1, D).expand(Hq, D), _f(wk).reshape(1, D).expand(Hkv, D)], 0)
+
+
+def qknorm_rope_fwd(qkv2d, wq, wk, cos, sin, T, Hq, Hkv, D, eps):
+    """QK-norm fused with RoPE, in place on the q|k columns: per row and head x -> RMSNorm over D with the q (k)
+    weight, then the rotate-half rotation of :func:`rope_` at position ``row mod T``, all in fp32 with ONE rounding.
+    The V columns are not touched.  Returns ``raw``, a contiguous copy of the q|k columns as they were (the backward
+    recomputes rstd from it; the in-place result cannot be inverted bit-safely)."""
+    N = qkv2d.shape[0]
+    heads, half = Hq + Hkv, D // 2
+    raw = qkv2d[:, :heads * D].clone().contiguous()
+    x = _f(raw).view(N // T, T, heads, D)
+    rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+    y = x * rstd * _qk_weight(wq, wk, Hq, Hkv, D)
+    y1, y2 = y[..., :half], y[..., half:]
+    c = cos[:T].view(1, T, 1, half)
+    s = sin[:T].view(1, T, 1, half)
+    o1 = y1 * c - y2 * s
+    o2 = y2 * c + y1 * s
+    qkv2d[:, :heads * D] = torch.cat([o1, o2], -1).reshape(N, heads * D).to(qkv2d.dtype)
+    return raw
+
+
+def qknorm_rope_bwd_(dqkv2d, raw, wq, wk, cos, sin, T, Hq, Hkv, D, eps):
+    """The backward of :func:`qknorm_rope_fwd`, in place on the q|k columns of ``dqkv2d``: g = R(-theta) dy in fp32,
+    rstd recomputed from ``raw`` by the forward's expression, xh = x rstd, dx = rstd (g w - xh mean(g w xh)) rounded
+    once.  Returns the weight-gradient partials (dwq_part, dwk_part), fp32 [1, D] each here (the GPU kernel returns
+    one row per workgroup): g xh summed over the rows and the q (k) heads."""
+    N = dqkv2d.shape[0]
+    heads, half = Hq + Hkv, D // 2
+    dy = _f(dqkv2d[:, :heads * D]).view(N // T, T, heads, D)
+    d1, d2 = dy[..., :half], dy[..., half:]
+    c = cos[:T].view(1, T, 1, half)
+    s = sin[:T].view(1, T, 1, half)
+    g = torch.cat([d1 * c + d2 * s, d2 * c - d1 * s], -1)
+    x = _f(raw).view(N // T, T, heads, D)
+    rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+    xh = x * rstd
+    gw = g * _qk_weight(wq, wk, Hq, Hkv, D)
+    dx = rstd * (gw - xh * (gw * xh).mean(-1, keepdim=True))
+    dqkv2d[:, :heads * D] = dx.reshape(N, heads * D).to(dqkv2d.dtype)
+    t = (g * xh).reshape(N, heads, D)
+    return t[:, :Hq].sum((0, 1)).reshape(1, D), t[:, Hq:].sum((0, 1)).reshape(1, D)
+
+
 # ------------------------------------------------------------------------------ embedding
 def embed_fwd(idx, wte, wpe, p, seed, site):
     B, T = idx.shape
