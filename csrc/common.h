@@ -201,3 +201,16 @@ DLTB_DEV int xcd_grouped(int L, int tiles) {
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Allow kernel Kern `bytes` of dynamic LDS (above the 64 KiB default).  The limit is a per-device attribute of the
+// kernel: set once per kernel and device this process launches on.
+template <auto Kern>
+void allow_dynamic_lds(int bytes) {
+  static bool done[64] = {};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const bool known = dev >= 0 && dev < 64;
+  if (known && done[dev]) return;
+  (void)hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (known) done[dev] = true;
+}

@@ -1,4 +1,4 @@
-// bf16 GEMM on MFMA for the transformer's linear layers (gfx950).
+// 16-bit GEMM on MFMA for the transformer's linear layers (gfx950); built for bf16 and for fp16 like every kernel file.
 //
 //   C[M, N] = sum_k A(m, k) B(k, n)   (+ bias[n])   (+ C  when accumulating)      fp32 accumulate
 //
@@ -110,6 +110,7 @@ __global__ __launch_bounds__(256, NSTAGE == 2 ? 2 : 1) void gemm_kernel(GemmArgs
   // next NSTAGE-2 stages stay in flight across the raw s_barrier.
   constexpr int GLDS = NPF + (TN ? (GldsTile<BM, kBK>::NI + GldsTile<BN, kBK>::NI)
                                 : (GldsTile<64, BM>::NI + GldsTile<64, BN>::NI));
+  static_assert(2 * GLDS < 64, "vmcnt range");
 #pragma unroll
   for (int st = 0; st < NSTAGE - 1; ++st)
     if (st < nk) load_stage(st, st);
@@ -180,12 +181,7 @@ __global__ __launch_bounds__(256, NSTAGE == 2 ? 2 : 1) void gemm_kernel(GemmArgs
 template <int BM, int BN, bool TN, bool PF, int NSTAGE>
 void launch_ns(const GemmArgs& g, int splits, hipStream_t st) {
   constexpr int smem = NSTAGE * Geo<BM, BN, TN>::STAGE + (PF ? 1024 : 0);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, TN, NSTAGE, PF>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr = true;
-  }
+  allow_dynamic_lds<gemm_kernel<BM, BN, TN, NSTAGE, PF>>(smem);
   const int tiles = (g.M / BM) * (g.N / BN);
   hipLaunchKernelGGL((gemm_kernel<BM, BN, TN, NSTAGE, PF>), dim3(tiles * splits), dim3(256), smem, st, g);
 }

@@ -208,17 +208,6 @@ __global__ __launch_bounds__(256, 1) void gemm_grouped_tn_kernel(GroupedTnArgs g
   store_tile(acc, dw, g.N, m0, n0, accumulate);
 }
 
-// the dynamic LDS limit is a per-device attribute of the kernel: set once per device this process launches on
-template <typename Kern>
-void allow_smem(Kern kern, bool (&done)[64]) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const bool known = dev >= 0 && dev < 64;
-  if (known && done[dev]) return;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-  if (known) done[dev] = true;
-}
-
 }  // namespace
 
 bool dltb_gemm_grouped_nt_supported(int R, int N, int K, int E) {
@@ -241,8 +230,7 @@ int dltb_gemm_grouped_nt(const void* a, const int* offsets, const void* const* b
   g.K = K;
   g.E = E;
   for (int e = 0; e < E; ++e) g.b[e] = (const bf16_t*)b[e];
-  static bool attr[64] = {};
-  allow_smem(gemm_grouped_nt_kernel, attr);
+  allow_dynamic_lds<gemm_grouped_nt_kernel>(SMEM_BYTES);
   hipLaunchKernelGGL(gemm_grouped_nt_kernel, dim3((R / BT) * (N / BT)), dim3(256), SMEM_BYTES, st, g);
   return 0;
 }
@@ -268,8 +256,7 @@ int dltb_gemm_grouped_tn(const void* dy, const void* x, const int* offsets, void
   g.E = E;
   g.accumulate = accumulate;
   for (int e = 0; e < E; ++e) g.dw[e] = (bf16_t*)dw[e];
-  static bool attr[64] = {};
-  allow_smem(gemm_grouped_tn_kernel, attr);
+  allow_dynamic_lds<gemm_grouped_tn_kernel>(SMEM_BYTES);
   hipLaunchKernelGGL(gemm_grouped_tn_kernel, dim3((M / BT) * (N / BT) * E), dim3(256), SMEM_BYTES, st, g);
   return 0;
 }

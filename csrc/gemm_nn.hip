@@ -83,6 +83,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nn_kernel(GemmArgs g) {
 
   // NSTAGE-deep ring, counted vmcnt across the raw s_barrier (gemm.hip)
   constexpr int GLDS = GldsTile<64, BM>::NI + GldsTile<BN, kBK>::NI;
+  static_assert(2 * GLDS < 64, "vmcnt range");
 #pragma unroll
   for (int st = 0; st < NSTAGE - 1; ++st)
     if (st < nk) load_stage(st, st);
@@ -138,14 +139,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nn_kernel(GemmArgs g) {
 template <int BM, int BN>
 void launch_nn(const GemmArgs& g, int splits, hipStream_t st) {
   constexpr int smem = GeoNN<BM, BN>::SMEM;
-  // the dynamic-LDS limit is a per-device attribute of the function: set it once per device
-  static bool attr[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr[dev]) {
-    (void)hipFuncSetAttribute((const void*)gemm_nn_kernel<BM, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (dev >= 0 && dev < 64) attr[dev] = true;
-  }
+  allow_dynamic_lds<gemm_nn_kernel<BM, BN>>(smem);
   const int tiles = (g.M / BM) * (g.N / BN);
   hipLaunchKernelGGL((gemm_nn_kernel<BM, BN>), dim3(tiles * splits), dim3(256), smem, st, g);
 }

@@ -438,12 +438,7 @@ template <int BM, int BN, int WGM, int D, bool M32, int NW = 4, int KG = 1, int 
 void launch_rsf(const RsArgs& g, hipStream_t st) {
   constexpr int smem = 3 * KG * RsGeo<BM, BN, WGM, D, M32, NW>::STAGE;
   static_assert(smem <= 163840, "LDS budget");
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_rsf_kernel<BM, BN, WGM, D, M32, NW, KG, STAG, DBG>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr = true;
-  }
+  allow_dynamic_lds<gemm_rsf_kernel<BM, BN, WGM, D, M32, NW, KG, STAG, DBG>>(smem);
   const int tiles = (g.M / BM) * (g.N / BN);
   hipLaunchKernelGGL((gemm_rsf_kernel<BM, BN, WGM, D, M32, NW, KG, STAG, DBG>), dim3(tiles), dim3(64 * NW * KG),
                      smem, st, g);

@@ -264,11 +264,7 @@ int dltb_gemm_tn(const void* a, const void* b, void* c, long lda, long ldb, long
   g.batch = batch;
   g.accumulate = accumulate;
   constexpr int smem = kRing3 * kStage3;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr = true;
-  }
+  allow_dynamic_lds<gemm_tn_kernel>(smem);
   const dim3 grid((unsigned)((long)(M / kTM) * (N / kTN) * batch));
   hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(512), smem, st, g);
   return 0;

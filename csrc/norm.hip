@@ -673,14 +673,7 @@ void launch_bwd_fused(int N, int d, hipStream_t st, const bf16_t* dy, const bf16
   constexpr int K = (RMS ? 1 : 2) + (XS ? 1 : 0);
   const size_t one = (size_t)K * kFusedWaves * d * sizeof(float);
   const bool one_fold = one <= kFoldLdsMax;
-  if (one_fold && one > 65536) {
-    static bool attr = false;                 // per instantiation: allow the large dynamic LDS image
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)norm_bwd_fused_kernel<NV, RMS, RES, XS>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFoldLdsMax);
-      attr = true;
-    }
-  }
+  if (one_fold && one > 65536) allow_dynamic_lds<norm_bwd_fused_kernel<NV, RMS, RES, XS>>((int)kFoldLdsMax);
   hipLaunchKernelGGL((norm_bwd_fused_kernel<NV, RMS, RES, XS>), dim3(dltb_norm_bwd_fused_blocks(N)),
                      dim3(kFusedWaves * 64), one_fold ? one : (size_t)kFusedWaves * d * sizeof(float), st, dy, s, w,
                      mean, rstd, dres, dx, part, N, d, rpw, fd.dm, fd.thr16, fd.scale, fd.seed, fd.site, one_fold);

@@ -268,6 +268,59 @@ def test_gemm(tn, M, N, K, cfg, splits, pf, gm, stages):
     close(acc, ref32 + prev.float(), 0.1, 2e-2, "gemm accumulate")
 
 
+GEMM_TILES = {0: (128, 128), 1: (256, 128), 2: (128, 256), 3: (128, 64), 4: (64, 128), 5: (64, 64)}
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("tn", [False, True], ids=["nt", "tn"])
+@pytest.mark.parametrize("cfg", sorted(GEMM_TILES))
+def test_gemm_exact_on_small_integers(dtype, tn, cfg):
+    """Operands, bias and the previous C in {-1, 0, 1}, alpha = 0.5: every fp32 sum is exact in any order and the
+    single rounding is torch's, so the kernel must equal the fp32 product bit for bit.  A stage read one k-step
+    early, or A and B fragments pairing different k, cannot hide in a tolerance.  2 x 2 tiles (gm 1 and 2: both
+    tile orders); K = 64 / 192 / 256 / 576 is 1 / 3 / 4 / 9 k-steps (a ring that never fills, that exactly fills at
+    depth 3 and 4, that wraps twice); deep ring and double buffer; with and without the L2 prefetch, whose distance
+    clamps at the last k-step; 3 splits of 3 k-steps through the reduce kernel; then 4 x 2 tiles, the count at which
+    the walk regroups XCD-major."""
+    C_ = ext()
+    BM, BN = GEMM_TILES[cfg]
+    M, N = 2 * BM, 2 * BN
+    if not C_.gemm_supported(M, N, 64, tn, cfg):
+        pytest.skip("tile config not offered for this layout")
+    gen = torch.Generator(device=DEV).manual_seed(7 + cfg)
+    ints = lambda *s: torch.randint(-1, 2, s, device=DEV, generator=gen).to(dtype)
+    bias, prev = ints(N), ints(M, N)
+    alpha = torch.tensor([0.5], device=DEV)
+    for K, splits in [(64, 1), (192, 1), (256, 1), (576, 1), (576, 3)]:
+        if tn:
+            a, b = ints(K, M + 64)[:, 64:], ints(K, N)                # strided view of a wider buffer
+            prod = a.float().t() @ b.float()
+        else:
+            a, b = ints(M, K + 64)[:, :K], ints(N, K)
+            prod = a.float() @ b.float().t()
+        want_bias = (prod * 0.5 + bias.float()).to(dtype)
+        want_acc = (prod * 0.5 + prev.float()).to(dtype)
+        for stages in (0, 2):
+            for pf in (0, 3):
+                what = f"K {K} splits {splits} stages {stages} pf {pf}"
+                got = C_.gemm(a, b, None, bias, tn, False, splits, cfg, pf, 1, alpha=alpha, stages=stages)
+                assert got.dtype == dtype and torch.equal(got, want_bias), what + ": alpha, bias"
+                acc = prev.clone()
+                C_.gemm(a, b, acc, None, tn, True, splits, cfg, pf, 2, alpha=alpha, stages=stages)
+                assert torch.equal(acc, want_acc), what + ": alpha, accumulate, gm 2"
+    # 4 x 2 tiles: the walk regroups a tile count that is a multiple of 8 (XCD-major), alone and under gm = 2
+    M, K = 4 * BM, 192
+    a, b = (ints(K, M), ints(K, N)) if tn else (ints(M, K), ints(N, K))
+    prev = ints(M, N)
+    prod = a.float().t() @ b.float() if tn else a.float() @ b.float().t()
+    for gm in (1, 2):
+        got = C_.gemm(a, b, None, bias, tn, False, 1, cfg, 0, gm)
+        assert torch.equal(got, (prod + bias.float()).to(dtype)), f"8 tiles, gm {gm}: bias"
+        acc = prev.clone()
+        C_.gemm(a, b, acc, None, tn, True, 1, cfg, 0, gm)
+        assert torch.equal(acc, (prod + prev.float()).to(dtype)), f"8 tiles, gm {gm}: accumulate"
+
+
 # superseded in both formats, against float64 with derived bounds, by tests/test_rowwise_gpu.py (kept as it is)
 def test_swiglu_rope():
     C = ext()

@@ -119,6 +119,51 @@ def test_gemm_grouped_nt(nt_inputs, K, N, dtype):
     assert torch.equal(fresh.view(torch.int16), got.view(torch.int16))
 
 
+INT_OFFSETS = [0, 128, 128, 384]             # 128, 0 and 256 rows; a tail of 128 rows
+INT_ROWS = INT_OFFSETS[-1] + 128
+
+
+def _ints(shape, gen, dtype):
+    return torch.randint(-1, 2, shape, generator=gen).to(DEV, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_gemm_grouped_nt_exact_on_small_integers(dtype):
+    """Entries in {-1, 0, 1}: every fp32 sum is exact in any order, so each segment must equal its fp32 product bit
+    for bit at 1 and 9 k-steps (a stage read early or a k-slice paired wrongly cannot hide in a bound)."""
+    gen = torch.Generator().manual_seed(47)
+    offsets = torch.tensor(INT_OFFSETS, dtype=torch.int32, device=DEV)
+    for K in (64, 576):
+        a = _ints((INT_ROWS, K), gen, dtype)
+        bs = [_ints((128, K), gen, dtype) for _ in INT_OFFSETS[1:]]
+        out = torch.full((INT_ROWS, 128), float("nan"), dtype=dtype, device=DEV)
+        F_.gemm_grouped_nt(a, offsets, bs, out)
+        want = torch.zeros_like(out)                                              # the tail: exact zeros
+        for e, b in enumerate(bs):
+            rows = slice(INT_OFFSETS[e], INT_OFFSETS[e + 1])
+            want[rows] = (a[rows].float() @ b.float().t()).to(dtype)
+        assert (a[INT_OFFSETS[-1]:] != 0).any() and torch.equal(out, want), f"K {K}"
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("empty_accumulates", [False, True])
+def test_gemm_grouped_tn_exact_on_small_integers(dtype, empty_accumulates):
+    """As above for the weight gradients: an accumulating group of 2 k-steps, an empty one (exact zeros, or its slot
+    untouched when accumulating) and an overwriting group of 4; the tail rows hold NaN and belong to nobody."""
+    gen = torch.Generator().manual_seed(53)
+    offsets = torch.tensor(INT_OFFSETS, dtype=torch.int32, device=DEV)
+    dy, x = _ints((INT_ROWS, 128), gen, dtype), _ints((INT_ROWS, 128), gen, dtype)
+    dy[INT_OFFSETS[-1]:] = float("nan")
+    old = [_ints((128, 128), gen, dtype) for _ in INT_OFFSETS[1:]]
+    acc = [True, empty_accumulates, False]
+    dws = [o.clone() for o in old]
+    F_.gemm_grouped_tn(dy, x, offsets, dws, acc)
+    for e, flag in enumerate(acc):
+        rows = slice(INT_OFFSETS[e], INT_OFFSETS[e + 1])
+        want = dy[rows].float().t() @ x[rows].float() + (old[e].float() if flag else 0.0)
+        assert torch.equal(dws[e], want.to(dtype)), f"group {e}, accumulate {flag}"
+
+
 def test_gemm_grouped_nt_refuses_what_it_cannot_run():
     off = torch.tensor([0, 128], dtype=torch.int32, device=DEV)
     mk = lambda r, c: torch.zeros(r, c, dtype=torch.bfloat16, device=DEV)
