@@ -93,6 +93,7 @@ struct AttnArgs {
                        // past the last query that sees key j); both non-decreasing along T, lo[i] <= i < hi[i]
   int q_begin, q_rows; // QR kernels: q / o / dout / dq / lse / delta hold only the q_rows queries at positions q_begin ..
                        // q_begin + q_rows - 1 of each batch row (multiples of kBlockRows); k / v / dk / dv hold all T rows
+  const bf16_t* sink;  // SINK forward kernels: [Hq] learned sink logits (raw, not multiplied by scale), 16-bit
 };
 
 // accumulator registers 8s .. 8s+7 -> bf16 B operand of k-step s
@@ -238,6 +239,12 @@ __global__ __launch_bounds__(256) void attn_doc_bounds_kernel(const int64_t* __r
 // splits without a visible tile; the rows without a key in a tile take the windowed softmax's NaN-safe paths.
 // The kernels trust the bounds: they are not validated on the device (no sync), only the tile range is clamped
 // to the sequence, so hand-made bounds that are not monotone or break lo[i] <= i < hi[i] give wrong results.
+// SINK (causal, no dropout, its own instantiations): one learned logit P.sink[hq] per query head joins the softmax
+// denominator and carries no value: lse = log(sum_j exp(z_j) + exp(sink)), O = sum_j p_j v_j with sum_j p_j < 1.
+// It enters once per query row in the epilogue, after the key loop and the key-split merge, as one more online-
+// softmax step without a V row.  A sink so negative that exp2 of it underflows to 0 leaves every bit of O and lse
+// as the sink-less kernel writes them (a = exp2(0) = 1, l + 0, 1 / l).  The backward kernels need no sink: they
+// rebuild p from this lse, and delta = rowsum(dO * O) keeps its meaning because the sink's value is the zero vector.
 constexpr float kRescaleLog2 = 8.f;
 
 template <int I>
@@ -353,9 +360,10 @@ constexpr int fwd_stage_bytes() { return 2 * kTile * D * 2 + 1024; }   // K, V, 
 template <int D, int KS = fwd_ks<D>()>
 constexpr int fwd_smem_bytes() { return fwd_nst<D, KS>() * KS * fwd_stage_bytes<D>(); }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false, bool SINK = false>
 __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !DROP) || !SINK, "a sink is causal and without dropout");
   static_assert((CAUSAL && !DROP) || !QR, "a query range is causal and without dropout (the packed mask is square)");
   static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
   constexpr bool BAND = WIN || DOC;     // rows / key splits may see no key of a visited tile
@@ -623,7 +631,16 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
     }
   }
   l += __shfl_xor(l, 32, 64);
-  const float inv = (DROP ? P.drop_scale : 1.f) / l;
+  float inv = (DROP ? P.drop_scale : 1.f) / l;
+  if constexpr (SINK) {
+    // every causal row sees at least its own key (also under WIN / DOC / QR), so m is finite here
+    const float s2 = bf2f(P.sink[hq]) * kLog2e;
+    const float mn = fmaxf(m, s2);
+    const float a = __builtin_amdgcn_exp2f(m - mn);
+    l = l * a + __builtin_amdgcn_exp2f(s2 - mn);
+    m = mn;
+    inv = a / l;
+  }
   bf16_t* orow = P.out + ((long)b * Tq + qi - qoff) * P.out_stride + hq * D;
   store_acc_rows<D>(orow, oacc, inv, h);
   if (h == 0) P.lse[((long)b * P.Hq + hq) * Tq + qi - qoff] = (m + __log2f(l)) * 0.69314718055994531f;
@@ -1318,12 +1335,34 @@ void set_attrs_qr() {
                             hipFuncAttributeMaxDynamicSharedMemorySize, dkdv_smem_bytes<D>());
 }
 
-template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false>
+// SINK = true: the forward instantiations with a learned sink (causal, no dropout; plain, WIN, DOC and their QR kinds),
+// with the key splits and the LDS ring of their sink-less twins.  The backward kernels have no sink instantiation.
+template <int D, bool WIN, bool DOC, bool QR>
+void set_attrs_sink() {
+  (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, true, false, fwd_ks<D, true>(), WIN, DOC, QR, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, fwd_smem_bytes<D, fwd_ks<D, true>()>());
+}
+
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false, bool SINK = false>
 void launch_fwd(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = fwd_ks<D, C>();
   constexpr int smem = fwd_smem_bytes<D, KS>();
   dim3 grid(((QR ? a.q_rows : a.T) / kBlockRows) * a.B * a.Hq);
-  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS, WIN, DOC, QR>), grid, dim3(256 * KS), smem, st, a);
+  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS, WIN, DOC, QR, SINK>), grid, dim3(256 * KS), smem, st, a);
+}
+
+// the sink forward (causal, no dropout): plain, windowed or with document bounds, the whole row or a query range
+template <int D>
+void launch_fwd_sink(const AttnArgs& a, hipStream_t st, bool win, bool doc, bool qr) {
+  if (qr) {
+    if (doc) launch_fwd<D, true, false, false, true, true, true>(a, st);
+    else if (win) launch_fwd<D, true, false, true, false, true, true>(a, st);
+    else launch_fwd<D, true, false, false, false, true, true>(a, st);
+  } else {
+    if (doc) launch_fwd<D, true, false, false, true, false, true>(a, st);
+    else if (win) launch_fwd<D, true, false, true, false, false, true>(a, st);
+    else launch_fwd<D, true, false, false, false, false, true>(a, st);
+  }
 }
 
 #define DLTB_ATTN_DISPATCH(FN, D, C, DR, ...)           \
@@ -1401,6 +1440,18 @@ void dltb_attn_init_attributes() {
   set_attrs_qr<128, false, false>();
   set_attrs_qr<128, true, false>();
   set_attrs_qr<128, false, true>();
+  set_attrs_sink<64, false, false, false>();
+  set_attrs_sink<64, true, false, false>();
+  set_attrs_sink<64, false, true, false>();
+  set_attrs_sink<64, false, false, true>();
+  set_attrs_sink<64, true, false, true>();
+  set_attrs_sink<64, false, true, true>();
+  set_attrs_sink<128, false, false, false>();
+  set_attrs_sink<128, true, false, false>();
+  set_attrs_sink<128, false, true, false>();
+  set_attrs_sink<128, false, false, true>();
+  set_attrs_sink<128, true, false, true>();
+  set_attrs_sink<128, false, true, true>();
 }
 
 void dltb_attn_doc_bounds(const int64_t* idx, int* bounds, int B, int T, int64_t eos, int window, hipStream_t st) {
@@ -1418,13 +1469,26 @@ void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const 
 void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
-                   hipStream_t st, int window, const int* bounds, int q_begin, int q_end) {
+                   hipStream_t st, int window, const int* bounds, int q_begin, int q_end, const void* sink) {
   AttnArgs a = make_args(q, k, v, qs, ks, vs, B, T, Hq, Hkv, scale, causal, thr16, drop_scale,
                          nullptr, 0);
   a.out = (bf16_t*)o;
   a.out_stride = os;
   a.lse = lse;
   a.mask = mask;
+  if (sink) {          // causal and thr16 == 0 (checked by the caller)
+    a.sink = (const bf16_t*)sink;
+    a.bounds = bounds;
+    a.window = windowed(causal, window, T) ? window : 0;
+    const bool qr = ranged(q_begin, q_end, T);
+    if (qr) {
+      a.q_begin = q_begin;
+      a.q_rows = q_end - q_begin;
+    }
+    if (D == 64) launch_fwd_sink<64>(a, st, a.window != 0, bounds != nullptr, qr);
+    else launch_fwd_sink<128>(a, st, a.window != 0, bounds != nullptr, qr);
+    return;
+  }
   if (ranged(q_begin, q_end, T)) {
     a.q_begin = q_begin;
     a.q_rows = q_end - q_begin;

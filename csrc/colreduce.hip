@@ -117,7 +117,16 @@ __global__ __launch_bounds__(256) void colreduce_multi_kernel(ColRedArgs A) {
   const int cq = threadIdx.x & 15, ph = threadIdx.x >> 4;
   const int c0 = blockIdx.x * 64 + cq * 4;
   float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (c0 < k) {
+  if (k & 3) {
+    // a width that is no multiple of 4 (the attention sinks of a model with 2 heads): the rows are not 16-byte
+    // aligned, so dword loads, each row phase summing its rows in order (segment-uniform branch)
+    float av[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (c0 + e < k)
+        for (int p = ph; p < S.P; p += 16) av[e] += S.part[(size_t)p * k + c0 + e];
+    a = make_float4(av[0], av[1], av[2], av[3]);
+  } else if (c0 < k) {
     // four partial rows in flight per lane (independent sums, added in a fixed order)
     float4 b[4];
 #pragma unroll

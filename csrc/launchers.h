@@ -128,7 +128,15 @@ void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* 
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
                    hipStream_t st, int window = 0, const int* bounds = nullptr, int q_begin = 0,
-                   int q_end = 0);
+                   int q_end = 0, const void* sink = nullptr);
+// sink (trailing, default absent): [Hq] learned sink logits in the build's 16-bit format (causal, thr16 == 0 only).
+// One raw logit per query head joins the softmax denominator and carries no value; o and lse include it, and the
+// backward kernels above take that lse and o unchanged.  attn_sink.hip forms the sink gradient from lse and delta:
+// part[g][h] = - sum over workgroup g's (b, t) rows of exp(sink[h] - lse[b, h, t]) * delta[b, h, t], fp32 [G][Hq]
+// with G = dltb_attn_sink_partials(B, Tq); every element of the G rows is written, no atomics, one fixed order.
+int dltb_attn_sink_partials(int B, int Tq);
+void dltb_attn_sink_bwd(const float* lse, const float* delta, const void* sink, float* part, int B, int Hq, int Tq,
+                        hipStream_t st);
 void dltb_attn_bwd_delta(const void* o, const void* dout, float* delta, long os, long dos, int B,
                          int T, int Hq, int D, hipStream_t st);
 void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, const void* dout,

@@ -15,7 +15,8 @@ Differences that make the numbers honest (recorded in the extended sidecar):
 Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device, --bucket-mb, --dropout, --seed,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
 --doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk, --moe-experts, --moe-top-k,
---moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef, --moe-dropless, --qk-norm.
+--moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef, --moe-dropless, --qk-norm,
+--attn-sinks.
 """
 import argparse
 import json
@@ -107,6 +108,10 @@ def build_parser():
                    help="causal tiers: RMSNorm over head_dim on every query and key head before RoPE, with one learned "
                         "[head_dim] weight for q and one for k per layer (Qwen3 / OLMo-2 / Gemma-3 style), fused with "
                         "RoPE into one pass; default: off")
+    p.add_argument("--attn-sinks", action="store_true",
+                   help="causal tiers: one learned sink logit per query head and layer that joins the attention "
+                        "softmax's denominator and carries no value (gpt-oss style), taken in by the forward "
+                        "attention kernel's epilogue; default: off")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -237,6 +242,17 @@ def check_qk_norm(on, mcfg, tier):
     mcfg.validate()
 
 
+def check_attn_sinks(on, mcfg, tier):
+    """ValueError when ``--attn-sinks`` is set for a tier without causal attention; sets it on ``mcfg``."""
+    if not on:
+        return
+    if not mcfg.causal:
+        raise ValueError(f"--attn-sinks needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the reference's "
+                         "non-causal attention with dropout")
+    mcfg.attn_sinks = True
+    mcfg.validate()
+
+
 def check_moe(experts, top_k, factor, recompute, mcfg, tier, aux_coef=None, z_coef=None, dropless=False):
     """ValueError when the ``--moe-*`` flags are set for a tier without the routed FFN or together with
     ``--activation-recompute``, or ``--moe-dropless`` together with an explicit ``--moe-capacity-factor``; sets them
@@ -348,6 +364,7 @@ def train(args):
                   getattr(args, "moe_aux_loss_coef", None), getattr(args, "moe_z_loss_coef", None),
                   bool(getattr(args, "moe_dropless", False)))
         check_qk_norm(bool(getattr(args, "qk_norm", False)), mcfg, args.tier)
+        check_attn_sinks(bool(getattr(args, "attn_sinks", False)), mcfg, args.tier)
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -379,6 +396,8 @@ def train(args):
                   f"{mcfg.moe_z_loss_coef}", flush=True)
         if mcfg.qk_norm and is_main:
             print(f"QK-norm: RMSNorm over head_dim {mcfg.head_dim} on q and k, fused with RoPE", flush=True)
+        if mcfg.attn_sinks and is_main:
+            print(f"attention sinks: one learned logit per query head ({mcfg.n_head} per layer)", flush=True)
         cp = None
         if cp_n > 1:
             cp = _context.ContextParallel(cp_n, cp_layout, mcfg.sliding_window, world, rank)
@@ -535,6 +554,7 @@ def train(args):
             "context_parallel": cp_n, "cp_layout": cp_layout if cp_n > 1 else None,
             "activation_recompute": recompute,
             "head_chunk": head_chunk, "head_chunks": n_head_chunks,
+            "attn_sinks": bool(mcfg.attn_sinks),
             # the last micro-step's assignments per layer and expert (before drops) and, with an auxiliary router
             # loss on, its per-layer values, read once, here
             "moe": model.moe_stats(head_rows) if mcfg.n_experts else None,
@@ -633,6 +653,7 @@ def main(argv=None):
         parser.error(str(e))
     try:
         check_qk_norm(args.qk_norm, get_model_config(args.tier, args.seq_len), args.tier)
+        check_attn_sinks(args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

@@ -56,6 +56,11 @@ class ModelConfig:
     # QK-norm (mistral arch): an RMSNorm over head_dim on every query head and every key head before RoPE, with one
     # learned [head_dim] weight for q and one for k per layer (eps = norm_eps); fused with RoPE (csrc/qknorm.hip)
     qk_norm: bool = False
+    # learned attention sinks (mistral arch): one raw logit per query head and layer that joins the softmax denominator
+    # and carries no value, so a head can attend to "nothing" (the gpt-oss block); parameter self_attn.sinks [n_head],
+    # initialised to zeros.  The forward kernel's epilogue takes it in (csrc/attention.hip SINK), csrc/attn_sink.hip
+    # forms its gradient.
+    attn_sinks: bool = False
 
     def __post_init__(self):
         self.validate()
@@ -81,6 +86,10 @@ class ModelConfig:
                 raise ValueError(f"qk_norm (QK-norm fused with RoPE) needs the mistral arch, got arch {self.arch!r}")
             if self.head_dim not in (64, 128):
                 raise ValueError(f"qk_norm needs head_dim 64 or 128, got {self.head_dim}")
+        if not isinstance(self.attn_sinks, bool):
+            raise ValueError(f"attn_sinks must be a bool, got {self.attn_sinks!r}")
+        if self.attn_sinks and self.arch != "mistral":
+            raise ValueError(f"attn_sinks (learned attention sinks) needs the mistral arch, got arch {self.arch!r}")
         k, cf = self.moe_top_k, self.moe_capacity_factor
         if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4):
             raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
@@ -150,6 +159,8 @@ class ModelConfig:
         per_block = d + (d * d + 2 * kvd * d) + d * d + d + ffn
         if self.qk_norm:         # the q and the k weight, [head_dim] each
             per_block += 2 * hd
+        if self.attn_sinks:      # one sink logit per query head
+            per_block += self.n_head
         head = 0 if self.tie_embeddings else V * d
         return V * d + L * per_block + d + head
 
@@ -160,7 +171,8 @@ class ModelConfig:
         tokens (a document mask depends on the data: ``SyntheticDataset.visible_pairs_per_row``); it replaces
         the T^2 / 2 (or window) count.  Without it the result is exactly the formula above.  With ``n_experts`` the
         FFN term counts ``moe_top_k`` experts and the router product per token.  ``qk_norm`` changes nothing here: it
-        adds no matrix product (its 2 * head_dim weights per layer are elementwise), like the other norms."""
+        adds no matrix product (its 2 * head_dim weights per layer are elementwise), like the other norms; nor does
+        ``attn_sinks`` (one more softmax term per query row and head)."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d

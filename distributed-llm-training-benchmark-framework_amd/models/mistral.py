@@ -28,6 +28,12 @@ With ``cfg.qk_norm`` every query head and every key head goes through an RMSNorm
 one learned [head_dim] weight for q and one for k per layer: ``self_attn.{q_norm,k_norm}.weight``, the LAST two
 entries of the layer's parameter list.  Norm and RoPE are one in-place pass (``qknorm_rope_fwd`` / ``_bwd_``,
 csrc/qknorm.hip) where the flag-off path runs ``rope_``; the forward keeps ``raw``, the q|k columns before the norm.
+
+With ``cfg.attn_sinks`` every query head has one learned sink logit per layer, ``self_attn.sinks`` [n_head], the LAST
+entry of the layer's parameter list (after the QK-norm pair when both are on).  It joins the softmax denominator of
+every query row and carries no value (``attn_fwd(..., sink=)``: the forward kernel's epilogue); o and lse include it,
+so nothing more is kept for the backward, whose kernels run unchanged; ``attn_bwd(..., sink=)`` adds one small
+reduction kernel whose fp32 partials reach the gradient slot with the layer's norm partials.
 """
 import math
 
@@ -47,13 +53,15 @@ class _RMSNorm(nn.Module):
 
 
 class _Attn(nn.Module):
-    def __init__(self, d, kvd, qk_norm_dim=None):
+    def __init__(self, d, kvd, qk_norm_dim=None, n_sinks=None):
         super().__init__()
         self.qkv_proj = nn.Linear(d, d + 2 * kvd, bias=False)
         self.o_proj = nn.Linear(d, d, bias=False)
         if qk_norm_dim:         # QK-norm: one [head_dim] weight for the query heads, one for the key heads
             self.q_norm = _RMSNorm(qk_norm_dim)
             self.k_norm = _RMSNorm(qk_norm_dim)
+        if n_sinks:             # attention sinks: one raw logit per query head
+            self.sinks = nn.Parameter(torch.zeros(n_sinks))
 
 
 class _MLP(nn.Module):
@@ -77,17 +85,22 @@ class MistralLayer(nn.Module):
         super().__init__()
         d = cfg.n_embd
         self.input_layernorm = _RMSNorm(d)
-        self.self_attn = _Attn(d, cfg.kv_heads * cfg.head_dim, cfg.head_dim if cfg.qk_norm else None)
+        self.self_attn = _Attn(d, cfg.kv_heads * cfg.head_dim, cfg.head_dim if cfg.qk_norm else None,
+                               cfg.n_head if cfg.attn_sinks else None)
         self.qk_norm = cfg.qk_norm
+        self.attn_sinks = cfg.attn_sinks
         self.post_attention_layernorm = _RMSNorm(d)
         self.mlp = _MoE(d, cfg.ffn_dim, cfg.n_experts) if cfg.n_experts else _MLP(d, cfg.ffn_dim)
 
     def param_list(self):
-        # the QK-norm weights come last, so the dense (4, 5) and MoE (4, 5 + 2e, 6 + 2e) indices hold with them
+        # the QK-norm weights and then the sinks come last, so the dense (4, 5) and MoE (4, 5 + 2e, 6 + 2e) indices
+        # hold with them
         tail = []
         if self.qk_norm:
             tail = [("self_attn.q_norm.weight", self.self_attn.q_norm.weight),
                     ("self_attn.k_norm.weight", self.self_attn.k_norm.weight)]
+        if self.attn_sinks:
+            tail = tail + [("self_attn.sinks", self.self_attn.sinks)]
         head = [("input_layernorm.weight", self.input_layernorm.weight),
                 ("self_attn.qkv_proj.weight", self.self_attn.qkv_proj.weight),
                 ("self_attn.o_proj.weight", self.self_attn.o_proj.weight),
@@ -124,8 +137,16 @@ class _EmbedFn(torch.autograd.Function):
 
 
 def _n_block_weights(cfg, ws):
-    """How many of a layer's parameters ``ws`` come before the QK-norm pair (the norms, projections and the FFN)."""
-    return len(ws) - (2 if cfg.qk_norm else 0)
+    """How many of a layer's parameters ``ws`` come before its tail -- the QK-norm pair, then the sinks -- that is
+    the norms, projections and the FFN."""
+    return len(ws) - (2 if cfg.qk_norm else 0) - (1 if cfg.attn_sinks else 0)
+
+
+def _attn_tail(cfg, ws):
+    """(nb, qkn, sink) of a layer's parameters ``ws``: :func:`_n_block_weights`, the QK-norm pair (q weight, k weight)
+    at nb, nb + 1 or None, and the sinks (the last parameter) or None."""
+    nb = _n_block_weights(cfg, ws)
+    return nb, (tuple(ws[nb:nb + 2]) if cfg.qk_norm else None), (ws[-1] if cfg.attn_sinks else None)
 
 
 def _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn):
@@ -172,11 +193,11 @@ def _cp_rope_gather(model, qkv, Hq, Hkv, D, qkn=None):
     return cp.gather_kv(qkv[:, Hq * D:], B, T), (raws if raws else None)
 
 
-def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed, qkn=None):
+def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed, qkn=None, sink=None):
     """Context-parallel attention forward (parallel/context.py): RoPE with each range's positions, all-gather of
     K | V into position order, then the range kernels -- the local queries of each range against all T keys.
     ``qkv`` holds the local tokens range-major, so a range's rows are one block.  Returns (o, lse per range, kv,
-    raw); ``qkn`` / ``raw``: :func:`_cp_rope_gather`."""
+    raw); ``qkn`` / ``raw``: :func:`_cp_rope_gather`; ``sink``: the layer's attention sinks for every range's call."""
     cp = model.cp
     B, T = model._cur_full_bt
     rngs = cp.ranges(T)
@@ -188,32 +209,39 @@ def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed, qkn=None):
     for j, rng in enumerate(rngs):
         _, lse, _ = F_.attn_fwd(qkv[j * n:(j + 1) * n, :qd], kv[:, :kd], kv[:, kd:], B, T, Hq, Hkv,
                                 1.0 / math.sqrt(D), True, 0.0, seed, 0, o_out=o[j * n:(j + 1) * n],
-                                window=window, bounds=bounds, q_range=rng)
+                                window=window, bounds=bounds, q_range=rng, sink=sink)
         lses.append(lse)
     return o, lses, kv, raw
 
 
 def _cp_attn_bwd(model, qkv, kv, o, do, lses, dqkv, Hq, Hkv, D, window, bounds, seed, qkn=None, raw=None, sq=None,
-                 sk=None, red=None):
+                 sk=None, red=None, sink=None, ss=None):
     """The backward of :func:`_cp_attn_fwd`: dQ of each range into its rows of ``dqkv``; each range's dK | dV
     over all T rows (zero where its queries see nothing), the zigzag pair summed by one add; reduce-scatter over
     the group into the local K | V columns of ``dqkv``; then the inverse RoPE of the local rows as without
     context parallelism.  With ``qkn`` = (wq, wk) the fused QK-norm + RoPE backward runs per range instead (``raw``:
     the forward's list); the ranges' weight-gradient partials fill one partial matrix per weight, so the later
-    ranges' sums accumulate onto the first's in the one fixed-order reduction into the slot ``sq`` / ``sk``."""
+    ranges' sums accumulate onto the first's in the one fixed-order reduction into the slot ``sq`` / ``sk``.  With
+    ``sink`` each range's call writes its own rows of one sink-gradient partial matrix, reduced once into ``ss``."""
     cp = model.cp
     B, T = model._cur_full_bt
     rngs = cp.ranges(T)
     n = qkv.shape[0] // len(rngs)
     qd, kd = Hq * D, Hkv * D
     dkv = None
+    spart, Gs = None, 0
+    if sink is not None:
+        Gs = F_.attn_sink_partials(dqkv, B, n // B)
+        spart = torch.empty(len(rngs) * Gs, Hq, dtype=torch.float32, device=dqkv.device)
     for j, rng in enumerate(rngs):
         part = torch.empty_like(kv)
         blk = slice(j * n, (j + 1) * n)
         F_.attn_bwd(qkv[blk, :qd], kv[:, :kd], kv[:, kd:], o[blk], do[blk], lses[j], None, dqkv[blk, :qd],
                     part[:, :kd], part[:, kd:], B, T, Hq, Hkv, 1.0 / math.sqrt(D), True, 0.0, seed, 0,
-                    window=window, bounds=bounds, q_range=rng)
+                    window=window, bounds=bounds, q_range=rng, sink=sink, part_out=spart, g_off=j * Gs)
         dkv = part if dkv is None else dkv.add_(part)
+    if sink is not None:
+        F_.reduce_partials(red, spart, ss[0], ss[1])
     cp.scatter_dkv(dkv, dqkv[:, qd:], B, T)       # waits for the reduce-scatter: the inverse RoPE reads it
     cos, sin = model.rope(qkv.device, T)
     if qkn is not None:
@@ -241,8 +269,7 @@ class _LayerFn(torch.autograd.Function):
                              f"(activation_recompute = {ctx.recompute!r}, n_experts = {cfg.n_experts})")
         ws = rt.acquire(unit)
         (w_in, wqkv, wo, w_post) = ws[:4]
-        nb = _n_block_weights(cfg, ws)
-        qkn = tuple(ws[nb:]) if cfg.qk_norm else None       # (q weight, k weight) of QK-norm
+        nb, qkn, sink = _attn_tail(cfg, ws)      # (q weight, k weight) of QK-norm; the attention sinks
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
         _, h1, _, rstd1 = F_.norm_fwd(x, None, w_in, None, cfg.norm_eps, True)
@@ -252,11 +279,12 @@ class _LayerFn(torch.autograd.Function):
         bounds = model._cur_bounds
         window = 0 if bounds is not None else cfg.sliding_window or 0
         if model.cp is not None:      # context parallel: local queries against the group's gathered K | V
-            o, lse, aux, raw = _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, rt.seed, qkn)
+            o, lse, aux, raw = _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, rt.seed, qkn, sink)
         else:
             raw = _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn)
             o, lse, aux = F_.attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
-                                      1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds)
+                                      1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds,
+                                      sink=sink)
         a = F_.linear_fwd(o, wo)
         x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
         ctx.moe = None
@@ -294,8 +322,7 @@ class _LayerFn(torch.autograd.Function):
         ws = rt.acquire_backward(unit)
         (w_in, wqkv, wo, w_post) = ws[:4]
         cfg = model.cfg
-        nb = _n_block_weights(cfg, ws)
-        qkn = tuple(ws[nb:]) if cfg.qk_norm else None
+        nb, qkn, sink = _attn_tail(cfg, ws)
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
         dx2 = dx2.contiguous()
@@ -320,11 +347,14 @@ class _LayerFn(torch.autograd.Function):
         window = 0 if ctx.bounds is not None else cfg.sliding_window or 0
         if model.cp is not None:      # aux: the gathered K | V of the forward
             _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed, qkn, raw,
-                         s[nb] if qkn else None, s[nb + 1] if qkn else None, red)
+                         s[nb] if qkn else None, s[nb + 1] if qkn else None, red, sink, s[-1])
         else:
-            F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
-                        dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
-                        1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds)
+            dsink = F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
+                                dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
+                                1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds,
+                                sink=sink)
+            if sink is not None:      # the sink-gradient partials join the layer's norm partials
+                F_.reduce_partials(red, dsink, s[-1][0], s[-1][1])
             _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, s[nb] if qkn else None, s[nb + 1] if qkn else None, red)
         ctx.bounds = None
         F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
@@ -488,6 +518,7 @@ def _layer_backward_recompute(ctx, dx2):
     * ``selective`` kept everything but the norm outputs h1, h2 and the SwiGLU output hh; they come back from
       elementwise kernels (``norm_apply`` from the kept row statistics, ``swiglu_bwd_h`` inside the SwiGLU backward).
     * with QK-norm both modes treat ``raw`` like qkv: ``selective`` keeps it, ``full`` rebuilds it with qkv.
+    * attention sinks keep nothing more in either mode: the kept o and lse already include the sink.
     * ``full`` kept x, o, lse.  The MLP half (a = o Wo^T, x1 / h2 / rstd2, gu) is rebuilt first and the attention
       half (h1 / rstd1, qkv + RoPE, under context parallelism the gathered K | V) only when the MLP half has been
       consumed and freed, so the rebuilt working set is half a layer's.  Attention itself and the down projection
@@ -504,13 +535,13 @@ def _layer_backward_recompute(ctx, dx2):
     ws = rt.acquire_backward(unit)
     (w_in, wqkv, wo, w_post, wgu, wd) = ws[:6]
     cfg = model.cfg
-    qkn = tuple(ws[6:]) if cfg.qk_norm else None            # the dense layer's QK-norm pair: parameters 6, 7
+    nb, qkn, sink = _attn_tail(cfg, ws)     # dense layer: nb = 6; the QK-norm pair at 6, 7, the sinks last
     B, T = model._cur_bt
     Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
     qd, kd = Hq * D, Hkv * D
     dx2 = dx2.contiguous()
     s = [rt.grad_slot(unit, j) for j in range(len(ws))]
-    sq, sk = (s[6], s[7]) if qkn else (None, None)
+    sq, sk = (s[nb], s[nb + 1]) if qkn else (None, None)
     # ---- MLP half
     if full:
         a = F_.linear_fwd(o, wo)
@@ -547,11 +578,14 @@ def _layer_backward_recompute(ctx, dx2):
         h1 = F_.norm_apply(x, w_in, None, None, rstd1, True)
     dqkv = torch.empty_like(qkv)
     if model.cp is not None:
-        _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed, qkn, raw, sq, sk, red)
+        _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed, qkn, raw, sq, sk, red,
+                     sink, s[-1])
     else:
-        F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
-                    dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
-                    1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds)
+        dsink = F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
+                            dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
+                            1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds, sink=sink)
+        if sink is not None:
+            F_.reduce_partials(red, dsink, s[-1][0], s[-1][1])
         _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, sq, sk, red)
     ctx.bounds = None
     del qkv, aux, o, do, lse, raw

@@ -5,6 +5,8 @@
 fused TinyGPT can be checked against it parameter-for-parameter (same state-dict names).  It is
 used only by tests and for parity checks; it is not a training path.
 """
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -132,6 +134,8 @@ class OracleMistral(nn.Module):
             if cfg.qk_norm:         # RMSNorm over head_dim of every q / k head before RoPE
                 layer.self_attn.q_norm = _RMSNorm(hd, cfg.norm_eps)
                 layer.self_attn.k_norm = _RMSNorm(hd, cfg.norm_eps)
+            if cfg.attn_sinks:      # one learned sink logit per query head
+                layer.self_attn.sinks = nn.Parameter(torch.zeros(cfg.n_head))
             layer.post_attention_layernorm = _RMSNorm(d, cfg.norm_eps)
             layer.mlp = nn.Module()
             if cfg.n_experts:       # mixture of experts: a router and n_experts FFNs (autograd only, _moe_ffn)
@@ -170,7 +174,7 @@ class OracleMistral(nn.Module):
             q, k = _rope(q, cos, sin), _rope(k, cos, sin)
             k = k.repeat_interleave(H // Hkv, 1)
             v = v.repeat_interleave(H // Hkv, 1)
-            if cfg.sliding_window or cfg.doc_eos_id is not None:
+            if cfg.sliding_window or cfg.doc_eos_id is not None or cfg.attn_sinks:
                 i = torch.arange(T, device=idx.device)
                 band = (i[None, :] <= i[:, None]).expand(B, 1, T, T)
                 if cfg.sliding_window:      # band mask: query i sees keys i - W < j <= i
@@ -180,7 +184,15 @@ class OracleMistral(nn.Module):
                     eos = (idx == cfg.doc_eos_id).to(torch.int64)
                     doc = eos.cumsum(1) - eos
                     band = band & (doc[:, None, :, None] == doc[:, None, None, :])
-                o = F.scaled_dot_product_attention(q, k, v, attn_mask=band)
+                if cfg.attn_sinks:
+                    # explicit softmax over [scores | sink]: the sink is one more column per head, raw (not scaled),
+                    # and carries no value, so its column is dropped before the product with v
+                    sc = (q @ k.transpose(-1, -2)) / math.sqrt(hd)
+                    sc = sc.masked_fill(~band, float("-inf"))
+                    sk = layer.self_attn.sinks.to(sc.dtype).view(1, H, 1, 1).expand(B, H, T, 1)
+                    o = torch.softmax(torch.cat([sc, sk], -1), -1)[..., :T] @ v
+                else:
+                    o = F.scaled_dot_product_attention(q, k, v, attn_mask=band)
             else:
                 o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
             x = x + layer.self_attn.o_proj(o.transpose(1, 2).reshape(B, T, H * hd))

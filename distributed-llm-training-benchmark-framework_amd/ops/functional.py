@@ -677,24 +677,33 @@ def doc_bounds(idx, eos_id, window=0):
 
 
 def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, mask=None, o_out=None, window=0, bounds=None,
-             q_range=None):
+             q_range=None, sink=None):
     """Returns (o, lse, aux); ``aux`` (the packed dropout mask on the GPU) goes back into attn_bwd.
     ``window`` = W > 0 (causal only): query i sees keys ``i - W < j <= i``; 0 = no window.
     ``bounds`` (causal only, with ``window=0``): the document bounds of :func:`doc_bounds`; query i sees keys
     ``bounds[0, b, i] <= j <= i``.  Hand-made bounds must keep its invariants: the kernels do not check them.
     ``q_range`` = (q_begin, q_end), multiples of 128 (causal only, p = 0 unless it is (0, T)): q, o and lse hold
     only those query rows of each batch row, k and v all T; masks, window and bounds keep meaning global
-    positions (:func:`ref.check_q_range`).  ``None`` or (0, T): the whole row, today's kernels."""
+    positions (:func:`ref.check_q_range`).  ``None`` or (0, T): the whole row, today's kernels.
+    ``sink`` ([Hq], q's dtype; causal only, p = 0): learned attention sinks, one raw logit per query head (not
+    multiplied by ``scale``) that joins the softmax denominator and carries no value: ``lse = log(sum_j exp(z_j) +
+    exp(sink))`` and the probabilities of a row sum to less than 1 (:func:`ref.check_sink`).  ``None``: no sink,
+    the same launches as ever."""
     ref.check_window(window, causal)
     ref.check_bounds(bounds, causal, window, B, T)
+    ref.check_sink(sink, q, Hq, causal, p)
     q_range = _q_range(q_range, T, causal, p)
     if _gpu(q):
         if p > 0 and mask is None:
             mask = ext().attn_mask(B, T, Hq, p, seed.device_tensor, site, q)
-        o, lse = ext().attn_fwd(q, k, v, mask if p > 0 else None, B, T, Hq, Hkv, scale, causal, p, o_out,
-                                window, bounds, q_range)
+        if sink is None:
+            o, lse = ext().attn_fwd(q, k, v, mask if p > 0 else None, B, T, Hq, Hkv, scale, causal, p, o_out,
+                                    window, bounds, q_range)
+        else:
+            o, lse = ext().attn_fwd(q, k, v, None, B, T, Hq, Hkv, scale, causal, p, o_out, window, bounds, q_range,
+                                    sink)
         return o, lse, (mask if p > 0 else None)
-    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window, bounds, q_range)
+    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window, bounds, q_range, sink)
     return _into(o_out, o), lse, None
 
 
@@ -704,13 +713,39 @@ def _q_range(q_range, T, causal, p):
     return None if (qb, qe) == (0, T) else (qb, qe)
 
 
+def attn_sink_partials(like, B, Tq):
+    """Rows of one :func:`attn_bwd` call's sink-gradient partials for B rows of Tq queries on ``like``'s device (a
+    function of (B, Tq) only)."""
+    return ext().attn_sink_partials(B, Tq) if _gpu(like) else 1
+
+
+def attn_sink_bwd(lse, delta, sink, part_out=None, g_off=0):
+    """The sink gradient from fp32 ``lse`` / ``delta`` [B, Hq, Tq] (csrc/attn_sink.hip): fp32 partials [G, Hq],
+    G = :func:`attn_sink_partials` (B, Tq), whose column sums are ``ds_h = - sum_{b, t} exp(sink_h - lse) delta``.
+    Every element of the G rows is written, without atomics and in one fixed order.  ``part_out`` (fp32 [Gtot, Hq])
+    and ``g_off``: write them at row ``g_off`` of a larger partial matrix.  Returns the G rows."""
+    if _gpu(lse):
+        part = ext().attn_sink_bwd(lse, delta, sink, part_out, g_off)
+        G = ext().attn_sink_partials(lse.shape[0], lse.shape[2])
+        return part[g_off:g_off + G]
+    ds = ref.attn_sink_bwd(lse, delta, sink)
+    if part_out is not None:
+        part_out[g_off:g_off + 1].copy_(ds)
+    return ds
+
+
 def attn_bwd(q, k, v, o, do, lse, aux, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0,
-             bounds=None, q_range=None):
+             bounds=None, q_range=None, sink=None, part_out=None, g_off=0):
     """dQ (query-major kernel, which also forms delta = rowsum(dO * O) for its rows), then dK/dV
     (key-major kernel, reading that delta).  ``window``, ``bounds``, ``q_range``: as in :func:`attn_fwd`; with a
-    range dk / dv (all T rows) receive the range's contribution and zeros in every row none of its queries sees."""
+    range dk / dv (all T rows) receive the range's contribution and zeros in every row none of its queries sees.
+    ``sink``: the forward's sinks; ``o`` and ``lse`` are the forward's (they include the sink), the two kernels run
+    unchanged, and :func:`attn_sink_bwd` then forms the sink-gradient partials from ``lse`` and the dQ pass's delta.
+    Returns those rows ([G, Hq] fp32, for :func:`reduce_partials`; ``part_out`` / ``g_off`` as there), None without
+    a sink."""
     ref.check_window(window, causal)
     ref.check_bounds(bounds, causal, window, B, T)
+    ref.check_sink(sink, q, Hq, causal, p)
     q_range = _q_range(q_range, T, causal, p)
     if _gpu(q):
         C = ext()
@@ -720,9 +755,14 @@ def attn_bwd(q, k, v, o, do, lse, aux, dq, dk, dv, B, T, Hq, Hkv, scale, causal,
                         bounds, q_range)
         C.attn_bwd_part(0, q, k, v, do, lse, delta, m, dk, dv, B, T, Hq, Hkv, scale, causal, p, None, window,
                         bounds, q_range)
-    else:
-        ref.attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window,
-                     bounds, q_range)
+        if sink is not None:
+            return attn_sink_bwd(lse, delta, sink, part_out, g_off)
+        return None
+    ds = ref.attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window,
+                      bounds, q_range, sink)
+    if ds is not None and part_out is not None:
+        part_out[g_off:g_off + 1].copy_(ds)
+    return ds
 
 
 # ------------------------------------------------------------------------------ linear

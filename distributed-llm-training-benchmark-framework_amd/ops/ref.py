@@ -323,6 +323,20 @@ def check_q_range(q_range, T, causal, p):
     return qb, qe
 
 
+def check_sink(sink, q, Hq, causal, p):
+    """ValueError unless ``sink`` is None or [Hq] values of q's dtype under the causal mask without dropout."""
+    if sink is None:
+        return
+    if not causal:
+        raise ValueError("attention: a sink needs causal=True")
+    if p != 0.0:
+        raise ValueError(f"attention: a sink needs dropout p = 0, got {p}")
+    if sink.numel() != Hq:
+        raise ValueError(f"attention: sink must hold Hq = {Hq} values, got {sink.numel()}")
+    if sink.dtype != q.dtype:
+        raise ValueError(f"attention: sink must have q's dtype {q.dtype}, got {sink.dtype}")
+
+
 def doc_bounds(idx, eos_id, window=0):
     """Document mask of packed rows as two int32 planes ``[2, B, T]``.  A token equal to ``eos_id`` ends a
     document and belongs to it.  ``lo[b, i]`` is the first key query i sees (0 without an EOS in ``idx[b, :i]``,
@@ -379,13 +393,20 @@ def _attn_keep(B, Hq, T, p, seed, site, device):
     return attn_keep_mask(s, rows, cols, p).view(B, Hq, T, T)
 
 
-def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0, bounds=None, q_range=None):
+def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0, bounds=None, q_range=None, sink=None):
     """``q_range`` (:func:`check_q_range`): q holds only the range's rows of each batch row; o [B * Tq, Hq * D]
-    and lse [B, Hq, Tq] come back for those rows."""
+    and lse [B, Hq, Tq] come back for those rows.  ``sink`` ([Hq], :func:`check_sink`): one raw logit per query head
+    is appended to every row's scores as a column without a value: the log-sum-exp runs over [scores | sink], the
+    probabilities of the real keys sum to less than 1."""
     D = q.shape[1] // Hq
     qb, qe = check_q_range(q_range, T, causal, p)
+    check_sink(sink, q, Hq, causal, p)
     s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds, qb, qe)
     lse = torch.logsumexp(s, -1)                                      # [B,Hq,T]
+    if sink is not None:
+        # log-sum-exp over the row with the sink column appended, as log(exp(lse of the scores) + exp(sink)): a sink
+        # whose exp underflows beside the row leaves lse as it was, to the bit
+        lse = torch.logaddexp(lse, _f(sink).to(lse.dtype).view(1, Hq, 1))
     pr = torch.exp(s - lse[..., None])
     keep = _attn_keep(B, Hq, T, p, seed, site, q.device)
     if keep is not None:
@@ -397,13 +418,24 @@ def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0, bou
     return o.to(q.dtype), _f(lse).contiguous()
 
 
+def attn_sink_bwd(lse, delta, sink):
+    """The sink gradient as partials [1, Hq] (the GPU kernel returns one row per workgroup):
+    ``ds_h = - sum_{b, t} exp(sink_h - lse[b, h, t]) * delta[b, h, t]`` with delta = rowsum(dO * O)."""
+    Hq = lse.shape[1]
+    sk = _f(sink).to(lse.dtype).view(1, Hq, 1)
+    return -(torch.exp(sk - lse) * delta.to(lse.dtype)).sum((0, 2)).reshape(1, Hq)
+
+
 def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0,
-             bounds=None, q_range=None):
+             bounds=None, q_range=None, sink=None):
     """``q_range``: q, o, do, lse, dq hold the range's rows; dk, dv all T rows -- the range's contribution, zero
-    in every row no query of the range sees."""
+    in every row no query of the range sees.  ``sink``: the forward's sinks; o and lse include them, so dq / dk / dv
+    are formed as without (p = exp(s - lse), delta = rowsum(dO * O): the sink's value is the zero vector) and the
+    sink gradient is returned as [1, Hq] partials (:func:`attn_sink_bwd`); None without a sink."""
     D = q.shape[1] // Hq
     G = Hq // Hkv
     qb, qe = check_q_range(q_range, T, causal, p)
+    check_sink(sink, q, Hq, causal, p)
     Tq = qe - qb
     s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds, qb, qe)
     pr = torch.exp(s - lse.view(B, Hq, Tq)[..., None])
@@ -427,6 +459,9 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, s
     dq.copy_(dqh.transpose(1, 2).reshape(B * Tq, Hq * D).to(dq.dtype))
     dk.copy_(dkh.transpose(1, 2).reshape(B * T, Hkv * D).to(dk.dtype))
     dv.copy_(dvh.transpose(1, 2).reshape(B * T, Hkv * D).to(dv.dtype))
+    if sink is None:
+        return None
+    return attn_sink_bwd(_f(lse).view(B, Hq, Tq), delta.squeeze(-1), sink)
 
 
 # ------------------------------------------------------------------------------ mixture of experts

@@ -6,6 +6,7 @@
     python scripts/bench_attn.py --doc-len 2048 [--window 4096]              # packed documents vs full causal
     python scripts/bench_attn.py --cp 8 --cp-layout zigzag [--window 4096]   # every rank's query ranges vs the whole row
     python scripts/bench_attn.py --q-range 0:2048 --q-range 30720:32768 --seq-lens 32768
+    python scripts/bench_attn.py --sinks --seq-lens 4096,16384 [--out profiles/attention_sinks.txt]
 
 Prints one line per kernel: time per call and TFLOP/s (causal FLOPs counted over the visible
 half).  Shapes: TinyGPT-A (B1 T2048 H16 D64, dropout 0.1, non-causal) and Mistral-7B
@@ -22,6 +23,11 @@ context-parallel group, dltb/parallel/context.py) times the three passes of each
 attention shape next to the whole-row call at the same ``--seq-lens`` length (and ``--window``), all alternating in
 one process as above, with the ratio of visited tiles (range / whole row).  With ``--cp`` it also prints every
 rank's summed time and the max / mean ratio over the ranks: the balance of the attention kernels of one step.
+
+``--sinks`` times the causal forward of the Mistral-7B attention shape with and without learned attention sinks
+(``attn_fwd(..., sink=)``: the SINK instantiation against its sink-less twin) at each ``--seq-lens`` length, full
+causal and with ``--sinks-window`` (default 4096), alternating in one process as above, plus the sink-gradient kernel
+``attn_sink_bwd``.  The yardstick is the sink-less call of the same run; ``--out`` also writes the lines to a file.
 """
 import argparse
 import json
@@ -221,6 +227,42 @@ def run_qrange(T, W, ranges, iters, rounds, B=1, Hq=32, Hkv=8, D=128, ranks=None
     return out
 
 
+def run_sinks(T, W, iters, rounds, B=1, Hq=32, Hkv=8, D=128, emit=print):
+    """The causal forward (window ``W``, 0 = full causal) without and with a sink, alternating over ``rounds`` rounds
+    after a warm-up round, and the sink-gradient kernel on the forward's lse and the dQ pass's delta."""
+    C = ext()
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    qkv = torch.randn(B * T, (Hq + 2 * Hkv) * D, device=dev, dtype=torch.bfloat16, generator=g)
+    q, k, v = qkv[:, :Hq * D], qkv[:, Hq * D:(Hq + Hkv) * D], qkv[:, (Hq + Hkv) * D:]
+    do = torch.randn(B * T, Hq * D, device=dev, dtype=torch.bfloat16, generator=g)
+    sink = (2.0 * torch.randn(Hq, device=dev, generator=g)).to(torch.bfloat16)
+    scale = D ** -0.5
+    o, lse = C.attn_fwd(q, k, v, None, B, T, Hq, Hkv, scale, True, 0.0, window=W, sink=sink)
+    delta = C.attn_bwd_delta(o, do, B, T, Hq)
+    fns = {"plain": lambda: C.attn_fwd(q, k, v, None, B, T, Hq, Hkv, scale, True, 0.0, window=W),
+           "sink": lambda: C.attn_fwd(q, k, v, None, B, T, Hq, Hkv, scale, True, 0.0, window=W, sink=sink),
+           "dsink": lambda: C.attn_sink_bwd(lse, delta, sink)}
+    times = {key: [] for key in fns}
+    for r in range(rounds + 1):                 # round 0 warms up; the sink-less and the sink call alternate
+        for key, fn in fns.items():
+            us = timeit(fn, iters)
+            if r:
+                times[key].append(us)
+    med = {key: sorted(t)[len(t) // 2] for key, t in times.items()}
+    lo, hi = min(times["plain"]), max(times["plain"])
+    ratio = med["sink"] / med["plain"]
+    inside = lo / med["plain"] <= ratio <= hi / med["plain"]
+    emit(f"T {T:6d} W {W:5d} fwd plain {med['plain']:9.1f} us ({lo:.1f} .. {hi:.1f})  "
+         f"sink {med['sink']:9.1f} us ({min(times['sink']):.1f} .. {max(times['sink']):.1f})  ratio {ratio:.4f}  "
+         f"plain spread {lo / med['plain']:.4f} .. {hi / med['plain']:.4f}  "
+         + ("inside the spread" if inside else "OUTSIDE THE SPREAD")
+         + f"  attn_sink_bwd {med['dsink']:6.1f} us ({min(times['dsink']):.1f} .. {max(times['dsink']):.1f}, "
+         f"{C.attn_sink_partials(B, T)} partial rows)")
+    return dict(plain_us=med["plain"], sink_us=med["sink"], ratio=ratio, plain_min=lo, plain_max=hi,
+                inside_spread=inside, dsink_us=med["dsink"])
+
+
 def doc_tile_counts(bounds, T):
     """tile_counts for document bounds [2, 1, T] (CPU): the tile ranges of the bounds kernels."""
     lo, hi = bounds[0, 0].tolist(), bounds[1, 0].tolist()
@@ -298,8 +340,30 @@ def main():
                     help="time this query range (multiples of 128) next to the whole row at --seq-lens; repeatable")
     ap.add_argument("--cp", type=int, default=0, help="shorthand: the query ranges of every rank of a group of N")
     ap.add_argument("--cp-layout", default="auto", choices=["auto", "contiguous", "zigzag"])
+    ap.add_argument("--sinks", action="store_true",
+                    help="time the causal forward with and without attention sinks, and the sink-gradient kernel")
+    ap.add_argument("--sinks-window", type=int, default=4096, help="the windowed variant of the --sinks comparison")
+    ap.add_argument("--out", default=None, help="--sinks: also write the result lines to this file")
     a = ap.parse_args()
-    if a.q_range or a.cp > 1:
+    if a.sinks:
+        lines = ["# scripts/bench_attn.py --sinks: the causal forward of the M7B head shape (B1 Hq32 Hkv8 D128, bf16) "
+                 "without and with learned attention sinks,",
+                 f"# medians of {a.rounds} interleaved rounds of {a.iters} calls in one process (min .. max in "
+                 "brackets); ratio = sink / plain; the yardstick is the",
+                 "# sink-less instantiation of the same run.  attn_sink_bwd: the sink-gradient kernel on [B, Hq, T] "
+                 "lse / delta.  One MI355X."]
+
+        def emit(line):
+            print(line, flush=True)
+            lines.append(line)
+        out = {}
+        for T in (int(x) for x in a.seq_lens.split(",")):
+            for W in (0, a.sinks_window):
+                out[f"T{T}_W{W}"] = run_sinks(T, W, a.iters, a.rounds, emit=emit)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+    elif a.q_range or a.cp > 1:
         from dltb.parallel import context as cpx
         out = {}
         for T in (int(x) for x in a.seq_lens.split(",")):
