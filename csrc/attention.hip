@@ -31,7 +31,8 @@
 // P pairs, attn_mask.h) and 2 in the backward.  The softmax scale c = scale * log2(e) is folded into
 // the operand each wave holds in registers (Q in the forward and dQ, K in dK/dV) and the row
 // constants (-m, -lse log2 e, -delta/s) are the S / dP chains' initial accumulators, so the score
-// tiles come out of the MFMAs as exp2 arguments.
+// tiles come out of the MFMAs as exp2 arguments.  (The soft-capped CAP instantiations can do neither -- a tanh sits
+// between the product and the exponent: see CAP in front of the forward kernel.)
 #include <cstdlib>
 
 // Softmax math is scalar f32: the file is built with -fno-slp-vectorize so the compiler does not
@@ -94,6 +95,7 @@ struct AttnArgs {
   int q_begin, q_rows; // QR kernels: q / o / dout / dq / lse / delta hold only the q_rows queries at positions q_begin ..
                        // q_begin + q_rows - 1 of each batch row (multiples of kBlockRows); k / v / dk / dv hold all T rows
   const bf16_t* sink;  // SINK forward kernels: [Hq] learned sink logits (raw, not multiplied by scale), 16-bit
+  float softcap;       // CAP kernels: every score x becomes softcap * tanh(x / softcap) before the masks (> 0; else unused)
 };
 
 // accumulator registers 8s .. 8s+7 -> bf16 B operand of k-step s
@@ -245,7 +247,34 @@ __global__ __launch_bounds__(256) void attn_doc_bounds_kernel(const int64_t* __r
 // softmax step without a V row.  A sink so negative that exp2 of it underflows to 0 leaves every bit of O and lse
 // as the sink-less kernel writes them (a = exp2(0) = 1, l + 0, 1 / l).  The backward kernels need no sink: they
 // rebuild p from this lse, and delta = rowsum(dO * O) keeps its meaning because the sink's value is the zero vector.
+// CAP (causal, no dropout, no sink; its own instantiations of all three kernels): logit soft-capping, every score
+// x = scale q.k becomes z = cap tanh(x / cap) before the masks and the softmax (P.softcap = cap > 0).  A nonlinear
+// function now sits between the product and the exponent, so the fold of the header does not apply: the S chain starts
+// from a zero accumulator and runs on the UNSCALED operands, so the MFMAs give the exact fp32 dot q.k of the 16-bit
+// inputs, and per score, with c = 2 log2(e) scale / cap,
+//   u = c (q.k),   e = exp2(u) = exp(2 x / cap),   r = rcp(1 + e),   t = tanh(x / cap) = 1 - 2 r.
+// The constant is NOT folded into the register-resident operand: rounding q c back to 16 bits moves x by about
+// 2^-9 |x| in bf16, which the plain kernels carry too, but where the cap is of the order of the scores that error
+// goes straight into z (CPU emulation of both forms at B2 T512 Hq8 Hkv2 D128 bf16, q scaled by 64, cap 2: the folded
+// form misses lse by up to 7.5x the GPU test's tolerance, the unfolded one by less than 0.001x).  One v_mul per score.
+// e = inf gives r = 0 and t = 1, e = 0 gives r = 1 and t = -1, both exactly, and every finite u gives a finite t
+// (1 + e >= 1: no 0 * inf, no inf - inf), so no score can turn into a NaN.  The exponent argument is
+// cap log2(e) t plus the row constant (-m in the forward, -lse log2(e) in the backward), one more fma per element;
+// the forward forms it as fma(-2 cap log2(e), r, cap log2(e) - m) without t itself.  The backward multiplies ds by
+// 1 - t^2 = fma(-t, t, 1) before it is packed (dQ: 4 (r - r^2), with the 4 in the row constant).  Cost per score over
+// the plain kernels: exp2 + rcp + mul + add + fma in the forward, exp2 + rcp + mul + add + 2-3 fma + mul in the
+// backward, and the row constant no longer rides in the accumulator.
+// Absolute error of a capped score z: v_exp_f32 and v_rcp_f32 are good to 1 ulp and 1 - 2 r rounds to 2^-24, so t is
+// off by at most about 2^-22 wherever it is evaluated (near 0, where tanh is small, as near +-1) and z by about
+// cap 2^-22: 1.2e-5 at cap 50, 0.24 at cap 1e6 -- this form is for caps of the order of the scores, not for a cap
+// that is meant to be off.  The lse that is stored is that of the capped scores; lazy rescale, BAND rows, the
+// key-split merge and the epilogue see capped scores and are unchanged.
 constexpr float kRescaleLog2 = 8.f;
+
+// r = 1 / (1 + exp(2 x / cap)) and t = tanh(x / cap) = 1 - 2 r from the raw dot d = q.k and c = 2 log2(e) scale / cap
+// (see CAP above): r is exactly 0 / 1 and t exactly +-1 when exp2 overflows / underflows
+DLTB_DEV float cap_rcp(float d, float c) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(d * c)); }
+DLTB_DEV float cap_tanh(float d, float c) { return __builtin_fmaf(-2.f, cap_rcp(d, c), 1.f); }
 
 template <int I>
 struct IC { static constexpr int value = I; constexpr operator int() const { return I; } };
@@ -360,9 +389,11 @@ constexpr int fwd_stage_bytes() { return 2 * kTile * D * 2 + 1024; }   // K, V, 
 template <int D, int KS = fwd_ks<D>()>
 constexpr int fwd_smem_bytes() { return fwd_nst<D, KS>() * KS * fwd_stage_bytes<D>(); }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false, bool SINK = false>
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false, bool SINK = false,
+          bool CAP = false>
 __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !DROP && !SINK) || !CAP, "soft-capping is causal, without dropout and without a sink");
   static_assert((CAUSAL && !DROP) || !SINK, "a sink is causal and without dropout");
   static_assert((CAUSAL && !DROP) || !QR, "a query range is causal and without dropout (the packed mask is square)");
   static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
@@ -388,9 +419,13 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
   {
     const bf16_t* qrow = P.q + ((long)b * Tq + qi - qoff) * P.q_stride + hq * D;
 #pragma unroll
-    for (int s = 0; s < D / 16; ++s)       // Q c: S' = (Q c) K^T is already in log2 units
-      qf[s] = scale_frag(__builtin_bit_cast(bfx8, ld16<uint4>(qrow + 16 * s + 8 * h)), P.scale * kLog2e);
+    for (int s = 0; s < D / 16; ++s) {     // Q c: S' = (Q c) K^T is already in log2 units (CAP: Q as it is)
+      qf[s] = __builtin_bit_cast(bfx8, ld16<uint4>(qrow + 16 * s + 8 * h));
+      if (!CAP) qf[s] = scale_frag(qf[s], P.scale * kLog2e);
+    }
   }
+  const float capl = CAP ? P.softcap * kLog2e : 0.f;                  // the cap in log2 units
+  const float capc = CAP ? 2.f * kLog2e * P.scale / P.softcap : 0.f;  // tanh argument per unit of q.k (see CAP)
   const int nt = CAUSAL ? min(nT, (qb * kBlockRows + kBlockRows - 1) / kTile + 1) : nT;
   // sliding window W: row qi sees keys qi - W < key <= qi, so the block's first row starts at key tile t_lo;
   // the key splits are numbered from there (t = t_lo + it * KS + split)
@@ -460,13 +495,20 @@ __global__ __launch_bounds__(256 * KS) void attn_fwd_kernel(AttnArgs P) {
     uint32_t ka[D / 16];
 #pragma unroll
     for (int s = 0; s < D / 16; ++s) ka[s] = lane_addr(kb, kfo[s]);
-    sacc[0] = mfma32(row_frag_at<0>(ka[0]), qf[0], mv);
-    sacc[1] = mfma32(row_frag_at<32 * D * 2>(ka[0]), qf[0], mv);
+    sacc[0] = mfma32(row_frag_at<0>(ka[0]), qf[0], CAP ? f32x16{} : mv);
+    sacc[1] = mfma32(row_frag_at<32 * D * 2>(ka[0]), qf[0], CAP ? f32x16{} : mv);
     static_for<D / 16 - 1>([&](auto S1) {
       constexpr int s = S1 + 1;
       sacc[0] = mfma32(row_frag_at<0>(ka[s]), qf[s], sacc[0]);
       sacc[1] = mfma32(row_frag_at<32 * D * 2>(ka[s]), qf[s], sacc[1]);
     });
+    if constexpr (CAP) {       // S' = cap log2(e) tanh(x / cap) - m from q.k, before the masks (mv is the splat of -m)
+      const float c0 = capl + mv[0], c1 = -2.f * capl;
+      static_for<32>([&](auto J) {
+        constexpr int n = J / 16, i = J % 16;
+        sacc[n][i] = __builtin_fmaf(c1, cap_rcp(sacc[n][i], capc), c0);
+      });
+    }
     if (CAUSAL && kv0 + kTile - 1 > q0) {      // diagonal tile: mask keys > query
 #pragma unroll
       for (int n = 0; n < 2; ++n)
@@ -755,9 +797,12 @@ DLTB_DEV void dkdv_finish(const AttnArgs& P, char* smem, f32x16 (&dk)[D / 32], f
   store_acc_rows<D>(dvrow, dv, s_drop, h);
 }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false>
+// CAP (see the forward): K stays unscaled, the S chain starts from zero and gives q.k; the softmax reads the row
+// constant -lse log2(e) from the stage, p = exp2(cap log2(e) t + it), and ds takes the factor 1 - t^2.
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false, bool CAP = false>
 __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !DROP) || !CAP, "soft-capping is causal and without dropout");
   static_assert((CAUSAL && !DROP) || !QR, "a query range is causal and without dropout (the packed mask is square)");
   static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
   constexpr int TB = kTile * D * 2;
@@ -806,10 +851,13 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
 #pragma unroll
     for (int s = 0; s < D / 16; ++s) {
       // K c: S' = Q (K c)^T - lse log2(e) is the exp2 argument itself (no multiply per score)
-      kf[s] = scale_frag(__builtin_bit_cast(bfx8, ld16<uint4>(krow + 16 * s + 8 * h)), P.scale * kLog2e);
+      kf[s] = __builtin_bit_cast(bfx8, ld16<uint4>(krow + 16 * s + 8 * h));
+      if (!CAP) kf[s] = scale_frag(kf[s], P.scale * kLog2e);
       vf[s] = __builtin_bit_cast(bfx8, ld16<uint4>(vrow + 16 * s + 8 * h));
     }
   }
+  const float capl = CAP ? P.softcap * kLog2e : 0.f;                  // the cap in log2 units
+  const float capc = CAP ? 2.f * kLog2e * P.scale / P.softcap : 0.f;  // tanh argument per unit of q.k
   f32x16 dk[NACC], dv[NACC];
 #pragma unroll
   for (int dt = 0; dt < NACC; ++dt) { dk[dt] = f32x16{}; dv[dt] = f32x16{}; }
@@ -902,8 +950,12 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int ql = 32 * mm + 8 * g4 + 4 * h;
-        const float4 L = *reinterpret_cast<const float4*>(lse2 + ql);
-        sa[4 * g4 + 0] = L.x; sa[4 * g4 + 1] = L.y; sa[4 * g4 + 2] = L.z; sa[4 * g4 + 3] = L.w;
+        if (CAP) {      // Q K^T from zero; the softmax adds the row constant
+          sa[4 * g4 + 0] = 0.f; sa[4 * g4 + 1] = 0.f; sa[4 * g4 + 2] = 0.f; sa[4 * g4 + 3] = 0.f;
+        } else {
+          const float4 L = *reinterpret_cast<const float4*>(lse2 + ql);
+          sa[4 * g4 + 0] = L.x; sa[4 * g4 + 1] = L.y; sa[4 * g4 + 2] = L.z; sa[4 * g4 + 3] = L.w;
+        }
         if (DROP) {
           dp[4 * g4 + 0] = 0.f; dp[4 * g4 + 1] = 0.f; dp[4 * g4 + 2] = 0.f; dp[4 * g4 + 3] = 0.f;
         } else {
@@ -945,10 +997,14 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
         }
         const float Dv[4] = {Dl.x, Dl.y, Dl.z, Dl.w};
         const uint32_t Mv[4] = {M4.x, M4.y, M4.z, M4.w};
+        float4 L4;
+        if (CAP) L4 = *reinterpret_cast<const float4*>(lse2 + ql);
+        const float Lv[4] = {L4.x, L4.y, L4.z, L4.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int i = 4 * g4 + e;
-          float p = __builtin_amdgcn_exp2f(sa[i]);
+          const float tc = CAP ? cap_tanh(sa[i], capc) : 0.f;
+          float p = __builtin_amdgcn_exp2f(CAP ? __builtin_fmaf(capl, tc, Lv[e]) : sa[i]);
           if (CAUSAL && diag && key > qb + 8 * g4 + 4 * h + e) p = 0.f;
           if (WIN && ledge && qb + 8 * g4 + 4 * h + e >= key + W) p = 0.f;
           if (DOC && ledge && qb + 8 * g4 + 4 * h + e >= hi_k) p = 0.f;
@@ -956,6 +1012,9 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dkdv_kernel(AttnArgs P) {
             const float pdv = __uint_as_float(__float_as_uint(p) & keep_mask_v(Mv[e], jbit));
             pd[i] = pdv;
             ds[i] = __builtin_fmaf(pdv, dp[i], p * Dv[e]);
+          } else if (CAP) {     // dx = dz (1 - t^2)
+            pd[i] = p;
+            ds[i] = p * dp[i] * __builtin_fmaf(-tc, tc, 1.f);
           } else {
             pd[i] = p;
             ds[i] = p * dp[i];
@@ -1064,9 +1123,12 @@ constexpr int dq_smem_bytes() {
   return ring > merge ? ring : merge;
 }
 
-template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false>
+// CAP (see the forward): Q stays unscaled, the S chain starts from zero and gives q.k;
+// p = exp2(cap log2(e) t - lse log2(e)) with the row constant applied per element, and ds takes the factor 1 - t^2.
+template <int D, bool CAUSAL, bool DROP, int KS, bool WIN = false, bool DOC = false, bool QR = false, bool CAP = false>
 __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   static_assert(CAUSAL || !WIN, "a window is a band under the causal diagonal");
+  static_assert((CAUSAL && !DROP) || !CAP, "soft-capping is causal and without dropout");
   static_assert((CAUSAL && !DROP) || !QR, "a query range is causal and without dropout (the packed mask is square)");
   static_assert((CAUSAL && !WIN) || !DOC, "document bounds are causal and carry the window themselves");
   constexpr int TB = kTile * D * 2;
@@ -1124,11 +1186,17 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
   }
   // row constants as the initial accumulators: S' = (Q c) K^T - lse log2(e) is the exp2 argument
   // and dP' = dO V^T - delta/s, so p = exp2(S'), dS = p (keep ? dP' : -delta/s)
-  const f32x16 nlv = splat16(-P.lse[bq * Tq + qi - qoff] * kLog2e);
+  const float nl = -P.lse[bq * Tq + qi - qoff] * kLog2e;
+  const f32x16 nlv = CAP ? f32x16{} : splat16(nl);      // CAP: q.k from zero, nl enters per element
   const float nd = -dlt * (DROP ? 1.f / P.drop_scale : 1.f);
   const f32x16 ndv = splat16(nd);
+  const float cap1 = CAP ? -2.f * P.softcap * kLog2e : 0.f;     // -2 cap log2(e)
+  const float cap0 = CAP ? P.softcap * kLog2e + nl + 2.f : 0.f;  // cap log2(e) - lse log2(e) + log2(4)
+  const float capc = CAP ? 2.f * kLog2e * P.scale / P.softcap : 0.f;   // tanh argument per unit of q.k
+  if constexpr (!CAP) {
 #pragma unroll
-  for (int s = 0; s < D / 16; ++s) qf[s] = scale_frag(qf[s], P.scale * kLog2e);   // after the delta dot
+    for (int s = 0; s < D / 16; ++s) qf[s] = scale_frag(qf[s], P.scale * kLog2e);   // after the delta dot
+  }
   const uint32_t* mbase = DROP ? P.mask + (long)bq * nT * 2 * T : nullptr;   // wave-uniform
   const uint32_t* mrow = DROP ? mbase + (long)h * T + qi : nullptr;
   const int nt = CAUSAL ? min(nT, (qb * kBlockRows + kBlockRows - 1) / kTile + 1) : nT;
@@ -1208,13 +1276,17 @@ __global__ __launch_bounds__(256 * KS) void attn_bwd_dq_kernel(AttnArgs P) {
       f32x16 ds;
       static_for<16>([&](auto I) {
         constexpr int i = I;
-        float p = __builtin_amdgcn_exp2f(sa[i]);
+        // CAP: p only feeds ds here, so everything is written in r = (1 - t) / 2: 4 p = exp2(c0 - 2 cap log2(e) r) with
+        // the 4 riding in the row constant, and 1 - t^2 = 4 (r - r^2), exactly 0 at r = 0 and r = 1
+        const float rc = CAP ? cap_rcp(sa[i], capc) : 0.f;
+        float p = __builtin_amdgcn_exp2f(CAP ? __builtin_fmaf(cap1, rc, cap0) : sa[i]);
         if (diag && kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h > qi) p = 0.f;
         if (ledge && kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h <= qi - W) p = 0.f;
         if (dedge && kv0 + 32 * n + (i & 3) + 8 * (i >> 2) + 4 * h < lo_q) p = 0.f;
         const float dpv = DROP ? (n == 0 ? keep_sel<mask_bit(0, i)>(dp[i], nd, mw)
                                          : keep_sel<mask_bit(1, i)>(dp[i], nd, mw)) : dp[i];
-        ds[i] = p * dpv;
+        if constexpr (CAP) ds[i] = p * dpv * __builtin_fmaf(-rc, rc, rc);      // dx = dz (1 - t^2) = (4 p) dP' (r - r^2)
+        else ds[i] = p * dpv;
       });
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
@@ -1343,13 +1415,32 @@ void set_attrs_sink() {
                             hipFuncAttributeMaxDynamicSharedMemorySize, fwd_smem_bytes<D, fwd_ks<D, true>()>());
 }
 
-template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false, bool SINK = false>
+// CAP = true: the soft-capped instantiations of the three kernels (causal, no dropout, no sink; plain, WIN, DOC and
+// their QR kinds), with the key splits and the LDS of their uncapped twins.  dQ at D = 64 stays at dq_ks splits for
+// every T (one instantiation per kind; the 3-split long-T variant has no capped twin).
+template <int D, bool WIN, bool DOC, bool QR>
+void set_attrs_cap() {
+  (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, true, false, fwd_ks<D, true>(), WIN, DOC, QR, false, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, fwd_smem_bytes<D, fwd_ks<D, true>()>());
+  constexpr int DQKS = DOC ? dq_ks_doc<D, false>() : dq_ks<D, true>();
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, true, false, DQKS, WIN, DOC, QR, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, dq_smem_bytes<D, DQKS>());
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<D, true, false, dkdv_ks<D>(), WIN, DOC, QR, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, dkdv_smem_bytes<D>());
+}
+
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false, bool SINK = false,
+          bool CAP = false>
 void launch_fwd(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = fwd_ks<D, C>();
   constexpr int smem = fwd_smem_bytes<D, KS>();
   dim3 grid(((QR ? a.q_rows : a.T) / kBlockRows) * a.B * a.Hq);
-  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS, WIN, DOC, QR, SINK>), grid, dim3(256 * KS), smem, st, a);
+  hipLaunchKernelGGL((attn_fwd_kernel<D, C, DR, KS, WIN, DOC, QR, SINK, CAP>), grid, dim3(256 * KS), smem, st, a);
 }
+
+// launch_fwd without a sink, with CAP in the backward launchers' position (for DLTB_ATTN_DISPATCH_CAP)
+template <int D, bool C, bool DR, bool WIN, bool DOC, bool QR, bool CAP>
+void launch_fwd_cap(const AttnArgs& a, hipStream_t st) { launch_fwd<D, C, DR, WIN, DOC, QR, false, CAP>(a, st); }
 
 // the sink forward (causal, no dropout): plain, windowed or with document bounds, the whole row or a query range
 template <int D>
@@ -1404,6 +1495,25 @@ void launch_fwd_sink(const AttnArgs& a, hipStream_t st, bool win, bool doc, bool
     }                                                   \
   } while (0)
 
+// the soft-capped (causal, no dropout, no sink) instantiations FN<D, true, false, WIN, DOC, QR, true>: plain, windowed
+// or with document bounds, the whole row or a query range
+#define DLTB_ATTN_CAP_KIND(FN, D, QR, WIN, DOC, ...)                          \
+  do {                                                                        \
+    if (DOC) FN<D, true, false, false, true, QR, true>(__VA_ARGS__);          \
+    else if (WIN) FN<D, true, false, true, false, QR, true>(__VA_ARGS__);     \
+    else FN<D, true, false, false, false, QR, true>(__VA_ARGS__);             \
+  } while (0)
+#define DLTB_ATTN_DISPATCH_CAP(FN, D, WIN, DOC, QR, ...)                      \
+  do {                                                                        \
+    if (D == 64) {                                                            \
+      if (QR) DLTB_ATTN_CAP_KIND(FN, 64, true, WIN, DOC, __VA_ARGS__);        \
+      else DLTB_ATTN_CAP_KIND(FN, 64, false, WIN, DOC, __VA_ARGS__);          \
+    } else {                                                                  \
+      if (QR) DLTB_ATTN_CAP_KIND(FN, 128, true, WIN, DOC, __VA_ARGS__);       \
+      else DLTB_ATTN_CAP_KIND(FN, 128, false, WIN, DOC, __VA_ARGS__);         \
+    }                                                                         \
+  } while (0)
+
 // A window of T or more keys is plain causal attention and runs the causal kernels (bitwise the same result);
 // only 0 < window < T takes the WIN instantiations.
 bool windowed(int causal, int window, int T) { return causal && window > 0 && window < T; }
@@ -1452,6 +1562,18 @@ void dltb_attn_init_attributes() {
   set_attrs_sink<128, false, false, true>();
   set_attrs_sink<128, true, false, true>();
   set_attrs_sink<128, false, true, true>();
+  set_attrs_cap<64, false, false, false>();
+  set_attrs_cap<64, true, false, false>();
+  set_attrs_cap<64, false, true, false>();
+  set_attrs_cap<64, false, false, true>();
+  set_attrs_cap<64, true, false, true>();
+  set_attrs_cap<64, false, true, true>();
+  set_attrs_cap<128, false, false, false>();
+  set_attrs_cap<128, true, false, false>();
+  set_attrs_cap<128, false, true, false>();
+  set_attrs_cap<128, false, false, true>();
+  set_attrs_cap<128, true, false, true>();
+  set_attrs_cap<128, false, true, true>();
 }
 
 void dltb_attn_doc_bounds(const int64_t* idx, int* bounds, int B, int T, int64_t eos, int window, hipStream_t st) {
@@ -1469,13 +1591,26 @@ void dltb_attn_mask(uint32_t* mask, int B, int T, int Hq, uint32_t thr16, const 
 void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
-                   hipStream_t st, int window, const int* bounds, int q_begin, int q_end, const void* sink) {
+                   hipStream_t st, int window, const int* bounds, int q_begin, int q_end, const void* sink,
+                   float softcap) {
   AttnArgs a = make_args(q, k, v, qs, ks, vs, B, T, Hq, Hkv, scale, causal, thr16, drop_scale,
                          nullptr, 0);
   a.out = (bf16_t*)o;
   a.out_stride = os;
   a.lse = lse;
   a.mask = mask;
+  if (softcap > 0.f) {  // causal, thr16 == 0 and no sink (checked by the caller)
+    a.softcap = softcap;
+    a.bounds = bounds;
+    a.window = windowed(causal, window, T) ? window : 0;
+    const bool qr = ranged(q_begin, q_end, T);
+    if (qr) {
+      a.q_begin = q_begin;
+      a.q_rows = q_end - q_begin;
+    }
+    DLTB_ATTN_DISPATCH_CAP(launch_fwd_cap, D, a.window != 0, bounds != nullptr, qr, a, st);
+    return;
+  }
   if (sink) {          // causal and thr16 == 0 (checked by the caller)
     a.sink = (const bf16_t*)sink;
     a.bounds = bounds;
@@ -1529,11 +1664,11 @@ void dltb_attn_bwd_delta(const void* o, const void* dout, float* delta, long os,
 }
 
 namespace {
-template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false>
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false, bool CAP = false>
 void launch_dkdv(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = dkdv_ks<D>();
   // QR: still one workgroup per key block of the whole row; those no query of the range sees store zeros
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, C, DR, KS, WIN, DOC, QR>), dim3((a.T / kBlockRows) * a.B * a.Hkv * a.gsplit),
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, C, DR, KS, WIN, DOC, QR, CAP>), dim3((a.T / kBlockRows) * a.B * a.Hkv * a.gsplit),
                      dim3(256 * KS), dkdv_smem_bytes<D>(), st, a);
   if (a.gsplit > 1) {
     const long rows = (long)a.B * a.T;
@@ -1542,10 +1677,10 @@ void launch_dkdv(const AttnArgs& a, hipStream_t st) {
                        a.part, a.gsplit, rows, cols, a.out, a.out_stride, a.out2, a.out2_stride);
   }
 }
-template <int D, bool C, bool DR, int KS, bool WIN, bool DOC, bool QR>
+template <int D, bool C, bool DR, int KS, bool WIN, bool DOC, bool QR, bool CAP = false>
 void launch_dq_ks(const AttnArgs& a, hipStream_t st) {
   constexpr int smem = dq_smem_bytes<D, KS>();
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, C, DR, KS, WIN, DOC, QR>),
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, C, DR, KS, WIN, DOC, QR, CAP>),
                      dim3(((QR ? a.q_rows : a.T) / kBlockRows) * a.B * a.Hq), dim3(256 * KS), smem, st, a);
 }
 // Causal D = 64 dQ: 2 key splits short, 3 from T = 1024 (A/B, profiles/attention_causal_d64_ks_r5.txt: T 2048
@@ -1556,13 +1691,14 @@ void launch_dq_ks(const AttnArgs& a, hipStream_t st) {
 constexpr int kDqCausalLongT = 1024;
 // A query range takes the splits of the whole row's kernel (by T, not by the range's length), so its rows come
 // out bit for bit as the whole row's.
-template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false>
+// The soft-capped kernels take dq_ks splits for every T (set_attrs_cap).
+template <int D, bool C, bool DR, bool WIN = false, bool DOC = false, bool QR = false, bool CAP = false>
 void launch_dq(const AttnArgs& a, hipStream_t st) {
   constexpr int KS = DOC ? dq_ks_doc<D, DR>() : dq_ks<D, C>();
-  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > KS && !(WIN && DR) && !DOC) {
+  if constexpr (D == 64 && C && DLTB_CAUSAL_KS_CAP && DLTB_DQ_KS64 > KS && !(WIN && DR) && !DOC && !CAP) {
     if (a.T >= kDqCausalLongT) return launch_dq_ks<D, C, DR, DLTB_DQ_KS64, WIN, DOC, QR>(a, st);
   }
-  launch_dq_ks<D, C, DR, KS, WIN, DOC, QR>(a, st);
+  launch_dq_ks<D, C, DR, KS, WIN, DOC, QR, CAP>(a, st);
 }
 }  // namespace
 
@@ -1609,7 +1745,8 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
                         void* out2, long qs, long ks, long vs, long dos, long outs, long out2s,
                         int B, int T, int Hq, int Hkv, int D, float scale, int causal,
                         uint32_t thr16, float drop_scale, hipStream_t st, const void* o, long os,
-                        int gsplit, float* part_buf, int window, const int* bounds, int q_begin, int q_end) {
+                        int gsplit, float* part_buf, int window, const int* bounds, int q_begin, int q_end,
+                        float softcap) {
   AttnArgs a = make_args(q, k, v, qs, ks, vs, B, T, Hq, Hkv, scale, causal, thr16, drop_scale,
                          nullptr, 0);
   if (part == 0 && gsplit > 1 && part_buf && (Hq / Hkv) % gsplit == 0) {
@@ -1627,6 +1764,21 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
   a.out2_stride = out2s;
   a.o = part == 1 ? (const bf16_t*)o : nullptr;     // dQ pass computes and writes delta itself
   a.o_stride = os;
+  if (softcap > 0.f) {  // causal and thr16 == 0 (checked by the caller)
+    a.softcap = softcap;
+    a.bounds = bounds;
+    a.window = windowed(causal, window, T) ? window : 0;
+    const bool qr = ranged(q_begin, q_end, T);
+    if (qr) {
+      a.q_begin = q_begin;
+      a.q_rows = q_end - q_begin;
+    }
+    if (part == 0)
+      DLTB_ATTN_DISPATCH_CAP(launch_dkdv, D, a.window != 0, bounds != nullptr, qr, a, st);
+    else
+      DLTB_ATTN_DISPATCH_CAP(launch_dq, D, a.window != 0, bounds != nullptr, qr, a, st);
+    return;
+  }
   if (ranged(q_begin, q_end, T)) {
     a.q_begin = q_begin;
     a.q_rows = q_end - q_begin;

@@ -128,7 +128,11 @@ void dltb_attn_fwd(const void* q, const void* k, const void* v, void* o, float* 
                    const uint32_t* mask, long qs, long ks, long vs, long os, int B, int T, int Hq,
                    int Hkv, int D, float scale, int causal, uint32_t thr16, float drop_scale,
                    hipStream_t st, int window = 0, const int* bounds = nullptr, int q_begin = 0,
-                   int q_end = 0, const void* sink = nullptr);
+                   int q_end = 0, const void* sink = nullptr, float softcap = 0.f);
+// softcap (trailing, default 0 = off; dltb_attn_fwd and dltb_attn_bwd_part): logit soft-capping, every score
+// x = scale q.k becomes softcap * tanh(x / softcap) before the masks and the softmax (causal, thr16 == 0, no sink:
+// the CAP instantiations of all three kernels).  lse is that of the capped scores; the backward recomputes the tanh
+// from the same product and saves nothing more.  With softcap == 0 the launches are exactly those without it.
 // sink (trailing, default absent): [Hq] learned sink logits in the build's 16-bit format (causal, thr16 == 0 only).
 // One raw logit per query head joins the softmax denominator and carries no value; o and lse include it, and the
 // backward kernels above take that lse and o unchanged.  attn_sink.hip forms the sink gradient from lse and delta:
@@ -145,7 +149,7 @@ void dltb_attn_bwd_part(int part, const void* q, const void* k, const void* v, c
                         int B, int T, int Hq, int Hkv, int D, float scale, int causal,
                         uint32_t thr16, float drop_scale, hipStream_t st, const void* o = nullptr,
                         long os = 0, int gsplit = 1, float* part_buf = nullptr, int window = 0,
-                        const int* bounds = nullptr, int q_begin = 0, int q_end = 0);
+                        const int* bounds = nullptr, int q_begin = 0, int q_end = 0, float softcap = 0.f);
 // dK/dV workgroups per KV head for a causal GQA backward (1 = one workgroup sums the whole group)
 int dltb_attn_dkdv_gsplit(int B, int T, int Hq, int Hkv, int causal, int window = 0, int bounds = 0);
 // document bounds of packed sequences: int32 [2][B][T] (lo plane, hi plane) from idx [B][T], one launch and no

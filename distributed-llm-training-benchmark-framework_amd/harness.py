@@ -16,7 +16,7 @@ Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
 --doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk, --moe-experts, --moe-top-k,
 --moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef, --moe-dropless, --qk-norm,
---attn-sinks.
+--attn-sinks, --attn-softcap.
 """
 import argparse
 import json
@@ -112,6 +112,10 @@ def build_parser():
                    help="causal tiers: one learned sink logit per query head and layer that joins the attention "
                         "softmax's denominator and carries no value (gpt-oss style), taken in by the forward "
                         "attention kernel's epilogue; default: off")
+    p.add_argument("--attn-softcap", type=float, default=0.0, metavar="C",
+                   help="causal tiers: attention logit soft-capping, every score x becomes C * tanh(x / C) before the "
+                        "softmax (Gemma-2 uses 50), in capped instantiations of the three attention kernels; not "
+                        "together with --attn-sinks; default: 0 = off")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -253,6 +257,23 @@ def check_attn_sinks(on, mcfg, tier):
     mcfg.validate()
 
 
+def check_attn_softcap(cap, sinks, mcfg, tier):
+    """ValueError when ``--attn-softcap`` is not a finite number >= 0, is set for a tier without causal attention or
+    together with ``--attn-sinks``; sets it on ``mcfg``."""
+    cap = float(cap or 0.0)
+    if cap == 0.0:
+        return
+    if not math.isfinite(cap) or cap < 0:
+        raise ValueError(f"--attn-softcap must be a finite number >= 0 (0 = off), got {cap}")
+    if not mcfg.causal:
+        raise ValueError(f"--attn-softcap needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the "
+                         "reference's non-causal attention with dropout")
+    if sinks:
+        raise ValueError("--attn-softcap together with --attn-sinks is not supported")
+    mcfg.attn_softcap = cap
+    mcfg.validate()
+
+
 def check_moe(experts, top_k, factor, recompute, mcfg, tier, aux_coef=None, z_coef=None, dropless=False):
     """ValueError when the ``--moe-*`` flags are set for a tier without the routed FFN or together with
     ``--activation-recompute``, or ``--moe-dropless`` together with an explicit ``--moe-capacity-factor``; sets them
@@ -365,6 +386,8 @@ def train(args):
                   bool(getattr(args, "moe_dropless", False)))
         check_qk_norm(bool(getattr(args, "qk_norm", False)), mcfg, args.tier)
         check_attn_sinks(bool(getattr(args, "attn_sinks", False)), mcfg, args.tier)
+        check_attn_softcap(getattr(args, "attn_softcap", 0.0), bool(getattr(args, "attn_sinks", False)), mcfg,
+                           args.tier)
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -398,6 +421,9 @@ def train(args):
             print(f"QK-norm: RMSNorm over head_dim {mcfg.head_dim} on q and k, fused with RoPE", flush=True)
         if mcfg.attn_sinks and is_main:
             print(f"attention sinks: one learned logit per query head ({mcfg.n_head} per layer)", flush=True)
+        if mcfg.attn_softcap and is_main:
+            print(f"attention soft-capping: scores capped to {mcfg.attn_softcap:g} * tanh(x / {mcfg.attn_softcap:g})",
+                  flush=True)
         cp = None
         if cp_n > 1:
             cp = _context.ContextParallel(cp_n, cp_layout, mcfg.sliding_window, world, rank)
@@ -555,6 +581,7 @@ def train(args):
             "activation_recompute": recompute,
             "head_chunk": head_chunk, "head_chunks": n_head_chunks,
             "attn_sinks": bool(mcfg.attn_sinks),
+            "attn_softcap": float(mcfg.attn_softcap),
             # the last micro-step's assignments per layer and expert (before drops) and, with an auxiliary router
             # loss on, its per-layer values, read once, here
             "moe": model.moe_stats(head_rows) if mcfg.n_experts else None,
@@ -654,6 +681,7 @@ def main(argv=None):
     try:
         check_qk_norm(args.qk_norm, get_model_config(args.tier, args.seq_len), args.tier)
         check_attn_sinks(args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
+        check_attn_softcap(args.attn_softcap, args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

@@ -13,6 +13,7 @@ Additional MI355X-era shape (not in the reference, requested by BASELINE.json co
 * ``M7B``: Mistral-7B shape - d 4096, 32 layers, 32 query heads / 8 KV heads (GQA), SwiGLU FFN 14336,
   RMSNorm, RoPE, causal attention, untied head, vocab 32000 (7.24B params).
 """
+import math
 from dataclasses import dataclass, field, asdict
 from typing import Optional
 
@@ -61,6 +62,10 @@ class ModelConfig:
     # initialised to zeros.  The forward kernel's epilogue takes it in (csrc/attention.hip SINK), csrc/attn_sink.hip
     # forms its gradient.
     attn_sinks: bool = False
+    # attention logit soft-capping (mistral arch): every score x = q.k / sqrt(head_dim) becomes cap * tanh(x / cap)
+    # before the masks and the softmax (Gemma-2 / Gemma-3 / Grok-1; Gemma-2 uses 50); 0 = off.  No parameter; the CAP
+    # instantiations of the three attention kernels (csrc/attention.hip).  Not together with attn_sinks.
+    attn_softcap: float = 0.0
 
     def __post_init__(self):
         self.validate()
@@ -90,6 +95,14 @@ class ModelConfig:
             raise ValueError(f"attn_sinks must be a bool, got {self.attn_sinks!r}")
         if self.attn_sinks and self.arch != "mistral":
             raise ValueError(f"attn_sinks (learned attention sinks) needs the mistral arch, got arch {self.arch!r}")
+        c = self.attn_softcap
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c < 0:
+            raise ValueError(f"attn_softcap must be a finite number >= 0 (0 = off), got {c!r}")
+        if c > 0 and self.arch != "mistral":
+            raise ValueError(f"attn_softcap (attention logit soft-capping) needs the mistral arch, got arch "
+                             f"{self.arch!r}")
+        if c > 0 and self.attn_sinks:
+            raise ValueError("attn_softcap together with attn_sinks is not supported")
         k, cf = self.moe_top_k, self.moe_capacity_factor
         if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4):
             raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
@@ -172,7 +185,8 @@ class ModelConfig:
         the T^2 / 2 (or window) count.  Without it the result is exactly the formula above.  With ``n_experts`` the
         FFN term counts ``moe_top_k`` experts and the router product per token.  ``qk_norm`` changes nothing here: it
         adds no matrix product (its 2 * head_dim weights per layer are elementwise), like the other norms; nor does
-        ``attn_sinks`` (one more softmax term per query row and head)."""
+        ``attn_sinks`` (one more softmax term per query row and head) or ``attn_softcap`` (elementwise on the
+        scores)."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d

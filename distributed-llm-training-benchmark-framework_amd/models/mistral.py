@@ -34,6 +34,11 @@ entry of the layer's parameter list (after the QK-norm pair when both are on).  
 every query row and carries no value (``attn_fwd(..., sink=)``: the forward kernel's epilogue); o and lse include it,
 so nothing more is kept for the backward, whose kernels run unchanged; ``attn_bwd(..., sink=)`` adds one small
 reduction kernel whose fp32 partials reach the gradient slot with the layer's norm partials.
+
+With ``cfg.attn_softcap`` = cap > 0 every attention score x becomes ``cap * tanh(x / cap)`` before the masks and the
+softmax (``attn_fwd`` / ``attn_bwd(..., softcap=)``: the CAP kernels of csrc/attention.hip) on every attention path --
+the whole row, the context-parallel ranges and both recompute modes.  It adds no parameter and keeps nothing more for
+the backward: lse is that of the capped scores and the backward kernels recompute the tanh.
 """
 import math
 
@@ -209,7 +214,8 @@ def _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, seed, qkn=None, sink=No
     for j, rng in enumerate(rngs):
         _, lse, _ = F_.attn_fwd(qkv[j * n:(j + 1) * n, :qd], kv[:, :kd], kv[:, kd:], B, T, Hq, Hkv,
                                 1.0 / math.sqrt(D), True, 0.0, seed, 0, o_out=o[j * n:(j + 1) * n],
-                                window=window, bounds=bounds, q_range=rng, sink=sink)
+                                window=window, bounds=bounds, q_range=rng, sink=sink,
+                                softcap=model.cfg.attn_softcap)
         lses.append(lse)
     return o, lses, kv, raw
 
@@ -238,7 +244,8 @@ def _cp_attn_bwd(model, qkv, kv, o, do, lses, dqkv, Hq, Hkv, D, window, bounds, 
         blk = slice(j * n, (j + 1) * n)
         F_.attn_bwd(qkv[blk, :qd], kv[:, :kd], kv[:, kd:], o[blk], do[blk], lses[j], None, dqkv[blk, :qd],
                     part[:, :kd], part[:, kd:], B, T, Hq, Hkv, 1.0 / math.sqrt(D), True, 0.0, seed, 0,
-                    window=window, bounds=bounds, q_range=rng, sink=sink, part_out=spart, g_off=j * Gs)
+                    window=window, bounds=bounds, q_range=rng, sink=sink, part_out=spart, g_off=j * Gs,
+                    softcap=model.cfg.attn_softcap)
         dkv = part if dkv is None else dkv.add_(part)
     if sink is not None:
         F_.reduce_partials(red, spart, ss[0], ss[1])
@@ -284,7 +291,7 @@ class _LayerFn(torch.autograd.Function):
             raw = _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn)
             o, lse, aux = F_.attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
                                       1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds,
-                                      sink=sink)
+                                      sink=sink, softcap=cfg.attn_softcap)
         a = F_.linear_fwd(o, wo)
         x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
         ctx.moe = None
@@ -352,7 +359,7 @@ class _LayerFn(torch.autograd.Function):
             dsink = F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                                 dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
                                 1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds,
-                                sink=sink)
+                                sink=sink, softcap=cfg.attn_softcap)
             if sink is not None:      # the sink-gradient partials join the layer's norm partials
                 F_.reduce_partials(red, dsink, s[-1][0], s[-1][1])
             _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, s[nb] if qkn else None, s[nb + 1] if qkn else None, red)
@@ -518,7 +525,8 @@ def _layer_backward_recompute(ctx, dx2):
     * ``selective`` kept everything but the norm outputs h1, h2 and the SwiGLU output hh; they come back from
       elementwise kernels (``norm_apply`` from the kept row statistics, ``swiglu_bwd_h`` inside the SwiGLU backward).
     * with QK-norm both modes treat ``raw`` like qkv: ``selective`` keeps it, ``full`` rebuilds it with qkv.
-    * attention sinks keep nothing more in either mode: the kept o and lse already include the sink.
+    * attention sinks keep nothing more in either mode: the kept o and lse already include the sink; nor does
+      ``attn_softcap`` (the kept lse is that of the capped scores).
     * ``full`` kept x, o, lse.  The MLP half (a = o Wo^T, x1 / h2 / rstd2, gu) is rebuilt first and the attention
       half (h1 / rstd1, qkv + RoPE, under context parallelism the gathered K | V) only when the MLP half has been
       consumed and freed, so the rebuilt working set is half a layer's.  Attention itself and the down projection
@@ -583,7 +591,8 @@ def _layer_backward_recompute(ctx, dx2):
     else:
         dsink = F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                             dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
-                            1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds, sink=sink)
+                            1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=ctx.bounds, sink=sink,
+                            softcap=cfg.attn_softcap)
         if sink is not None:
             F_.reduce_partials(red, dsink, s[-1][0], s[-1][1])
         _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, sq, sk, red)

@@ -174,7 +174,7 @@ class OracleMistral(nn.Module):
             q, k = _rope(q, cos, sin), _rope(k, cos, sin)
             k = k.repeat_interleave(H // Hkv, 1)
             v = v.repeat_interleave(H // Hkv, 1)
-            if cfg.sliding_window or cfg.doc_eos_id is not None or cfg.attn_sinks:
+            if cfg.sliding_window or cfg.doc_eos_id is not None or cfg.attn_sinks or cfg.attn_softcap:
                 i = torch.arange(T, device=idx.device)
                 band = (i[None, :] <= i[:, None]).expand(B, 1, T, T)
                 if cfg.sliding_window:      # band mask: query i sees keys i - W < j <= i
@@ -191,6 +191,11 @@ class OracleMistral(nn.Module):
                     sc = sc.masked_fill(~band, float("-inf"))
                     sk = layer.self_attn.sinks.to(sc.dtype).view(1, H, 1, 1).expand(B, H, T, 1)
                     o = torch.softmax(torch.cat([sc, sk], -1), -1)[..., :T] @ v
+                elif cfg.attn_softcap:
+                    # explicit softmax over the capped scores cap * tanh(x / cap); the masks apply after the cap
+                    sc = (q @ k.transpose(-1, -2)) / math.sqrt(hd)
+                    sc = cfg.attn_softcap * torch.tanh(sc / cfg.attn_softcap)
+                    o = torch.softmax(sc.masked_fill(~band, float("-inf")), -1) @ v
                 else:
                     o = F.scaled_dot_product_attention(q, k, v, attn_mask=band)
             else:

@@ -677,7 +677,7 @@ def doc_bounds(idx, eos_id, window=0):
 
 
 def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, mask=None, o_out=None, window=0, bounds=None,
-             q_range=None, sink=None):
+             q_range=None, sink=None, softcap=0.0):
     """Returns (o, lse, aux); ``aux`` (the packed dropout mask on the GPU) goes back into attn_bwd.
     ``window`` = W > 0 (causal only): query i sees keys ``i - W < j <= i``; 0 = no window.
     ``bounds`` (causal only, with ``window=0``): the document bounds of :func:`doc_bounds`; query i sees keys
@@ -688,22 +688,30 @@ def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, mask=None, o_
     ``sink`` ([Hq], q's dtype; causal only, p = 0): learned attention sinks, one raw logit per query head (not
     multiplied by ``scale``) that joins the softmax denominator and carries no value: ``lse = log(sum_j exp(z_j) +
     exp(sink))`` and the probabilities of a row sum to less than 1 (:func:`ref.check_sink`).  ``None``: no sink,
-    the same launches as ever."""
+    the same launches as ever.
+    ``softcap`` = cap > 0 (causal only, p = 0, no sink; :func:`ref.check_softcap`): logit soft-capping, every score
+    ``x = scale q.k`` becomes ``cap * tanh(x / cap)`` before the masks and the softmax (the CAP kernels of
+    csrc/attention.hip); ``lse`` is that of the capped scores.  0: off, the same launches as ever."""
     ref.check_window(window, causal)
     ref.check_bounds(bounds, causal, window, B, T)
     ref.check_sink(sink, q, Hq, causal, p)
+    ref.check_softcap(softcap, causal, p, sink)
     q_range = _q_range(q_range, T, causal, p)
     if _gpu(q):
         if p > 0 and mask is None:
             mask = ext().attn_mask(B, T, Hq, p, seed.device_tensor, site, q)
-        if sink is None:
+        if softcap:
+            o, lse = ext().attn_fwd(q, k, v, None, B, T, Hq, Hkv, scale, causal, p, o_out, window, bounds, q_range,
+                                    softcap=float(softcap))
+        elif sink is None:
             o, lse = ext().attn_fwd(q, k, v, mask if p > 0 else None, B, T, Hq, Hkv, scale, causal, p, o_out,
                                     window, bounds, q_range)
         else:
             o, lse = ext().attn_fwd(q, k, v, None, B, T, Hq, Hkv, scale, causal, p, o_out, window, bounds, q_range,
                                     sink)
         return o, lse, (mask if p > 0 else None)
-    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window, bounds, q_range, sink)
+    o, lse = ref.attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window, bounds, q_range, sink,
+                          softcap)
     return _into(o_out, o), lse, None
 
 
@@ -735,31 +743,35 @@ def attn_sink_bwd(lse, delta, sink, part_out=None, g_off=0):
 
 
 def attn_bwd(q, k, v, o, do, lse, aux, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0,
-             bounds=None, q_range=None, sink=None, part_out=None, g_off=0):
+             bounds=None, q_range=None, sink=None, part_out=None, g_off=0, softcap=0.0):
     """dQ (query-major kernel, which also forms delta = rowsum(dO * O) for its rows), then dK/dV
     (key-major kernel, reading that delta).  ``window``, ``bounds``, ``q_range``: as in :func:`attn_fwd`; with a
     range dk / dv (all T rows) receive the range's contribution and zeros in every row none of its queries sees.
     ``sink``: the forward's sinks; ``o`` and ``lse`` are the forward's (they include the sink), the two kernels run
     unchanged, and :func:`attn_sink_bwd` then forms the sink-gradient partials from ``lse`` and the dQ pass's delta.
     Returns those rows ([G, Hq] fp32, for :func:`reduce_partials`; ``part_out`` / ``g_off`` as there), None without
-    a sink."""
+    a sink.
+    ``softcap``: the forward's cap; ``lse`` is that of the capped scores and both kernels recompute the tanh from the
+    same product (their CAP instantiations), nothing more is saved.  0: off, the same launches as ever."""
     ref.check_window(window, causal)
     ref.check_bounds(bounds, causal, window, B, T)
     ref.check_sink(sink, q, Hq, causal, p)
+    ref.check_softcap(softcap, causal, p, sink)
     q_range = _q_range(q_range, T, causal, p)
     if _gpu(q):
         C = ext()
         m = aux if p > 0 else None
         delta = torch.empty_like(lse)
+        cap = {"softcap": float(softcap)} if softcap else {}
         C.attn_bwd_part(1, q, k, v, do, lse, delta, m, dq, None, B, T, Hq, Hkv, scale, causal, p, o, window,
-                        bounds, q_range)
+                        bounds, q_range, **cap)
         C.attn_bwd_part(0, q, k, v, do, lse, delta, m, dk, dv, B, T, Hq, Hkv, scale, causal, p, None, window,
-                        bounds, q_range)
+                        bounds, q_range, **cap)
         if sink is not None:
             return attn_sink_bwd(lse, delta, sink, part_out, g_off)
         return None
     ds = ref.attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window,
-                      bounds, q_range, sink)
+                      bounds, q_range, sink, softcap)
     if ds is not None and part_out is not None:
         part_out[g_off:g_off + 1].copy_(ds)
     return ds

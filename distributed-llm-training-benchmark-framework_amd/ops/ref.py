@@ -337,6 +337,22 @@ def check_sink(sink, q, Hq, causal, p):
         raise ValueError(f"attention: sink must have q's dtype {q.dtype}, got {sink.dtype}")
 
 
+def check_softcap(softcap, causal, p, sink):
+    """Logit soft-capping ``cap``: every score x becomes ``cap * tanh(x / cap)`` before the masks and the softmax
+    (Gemma-2 uses 50).  ValueError unless ``cap == 0`` (off), or ``cap`` is finite and > 0 under the causal mask,
+    without dropout and without a sink."""
+    if softcap == 0:
+        return
+    if not (isinstance(softcap, (int, float)) and math.isfinite(softcap) and softcap > 0):
+        raise ValueError(f"attention: softcap must be 0 (off) or finite and > 0, got {softcap!r}")
+    if not causal:
+        raise ValueError("attention: softcap needs causal=True")
+    if p != 0.0:
+        raise ValueError(f"attention: softcap needs dropout p = 0, got {p}")
+    if sink is not None:
+        raise ValueError("attention: softcap together with a sink is not supported")
+
+
 def doc_bounds(idx, eos_id, window=0):
     """Document mask of packed rows as two int32 planes ``[2, B, T]``.  A token equal to ``eos_id`` ends a
     document and belongs to it.  ``lo[b, i]`` is the first key query i sees (0 without an EOS in ``idx[b, :i]``,
@@ -362,8 +378,9 @@ def doc_bounds(idx, eos_id, window=0):
     return torch.stack([lo, hi]).to(torch.int32)
 
 
-def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0, bounds=None, qb=0, qe=None):
-    """Scores [B, Hq, Tq, T] of the queries at positions ``qb .. qe - 1`` (default: all T) against all T keys."""
+def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0, bounds=None, qb=0, qe=None, softcap=0.0):
+    """Scores [B, Hq, Tq, T] of the queries at positions ``qb .. qe - 1`` (default: all T) against all T keys.
+    ``softcap`` = cap > 0: the raw scores x are capped to ``cap * tanh(x / cap)`` before the masks."""
     check_window(window, causal)
     check_bounds(bounds, causal, window, B, T)
     qe = T if qe is None else qe
@@ -372,6 +389,8 @@ def _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window=0, bounds=None, qb
     if Hq != Hkv:
         kh = kh.repeat_interleave(Hq // Hkv, dim=1)
     s = torch.matmul(qh, kh.transpose(-1, -2)) * scale
+    if softcap:
+        s = softcap * torch.tanh(s / softcap)
     if causal:
         m = torch.ones(T, T, dtype=torch.bool, device=q.device).triu(1)
         if 0 < window < T:                                            # keys j <= i - W are out of the band
@@ -393,15 +412,18 @@ def _attn_keep(B, Hq, T, p, seed, site, device):
     return attn_keep_mask(s, rows, cols, p).view(B, Hq, T, T)
 
 
-def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0, bounds=None, q_range=None, sink=None):
+def attn_fwd(q, k, v, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0, bounds=None, q_range=None, sink=None,
+             softcap=0.0):
     """``q_range`` (:func:`check_q_range`): q holds only the range's rows of each batch row; o [B * Tq, Hq * D]
     and lse [B, Hq, Tq] come back for those rows.  ``sink`` ([Hq], :func:`check_sink`): one raw logit per query head
     is appended to every row's scores as a column without a value: the log-sum-exp runs over [scores | sink], the
-    probabilities of the real keys sum to less than 1."""
+    probabilities of the real keys sum to less than 1.  ``softcap`` (:func:`check_softcap`): the scores are capped
+    before the masks; lse is that of the capped scores."""
     D = q.shape[1] // Hq
     qb, qe = check_q_range(q_range, T, causal, p)
     check_sink(sink, q, Hq, causal, p)
-    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds, qb, qe)
+    check_softcap(softcap, causal, p, sink)
+    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds, qb, qe, softcap)
     lse = torch.logsumexp(s, -1)                                      # [B,Hq,T]
     if sink is not None:
         # log-sum-exp over the row with the sink column appended, as log(exp(lse of the scores) + exp(sink)): a sink
@@ -427,17 +449,20 @@ def attn_sink_bwd(lse, delta, sink):
 
 
 def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, seed, site, window=0,
-             bounds=None, q_range=None, sink=None):
+             bounds=None, q_range=None, sink=None, softcap=0.0):
     """``q_range``: q, o, do, lse, dq hold the range's rows; dk, dv all T rows -- the range's contribution, zero
     in every row no query of the range sees.  ``sink``: the forward's sinks; o and lse include them, so dq / dk / dv
     are formed as without (p = exp(s - lse), delta = rowsum(dO * O): the sink's value is the zero vector) and the
-    sink gradient is returned as [1, Hq] partials (:func:`attn_sink_bwd`); None without a sink."""
+    sink gradient is returned as [1, Hq] partials (:func:`attn_sink_bwd`); None without a sink.  ``softcap``: the
+    forward's cap; with z = cap tanh(x / cap), dz = p (dP - delta) as ever and dx = dz (1 - tanh(x / cap)^2), the
+    tanh recomputed from the same product (a masked score has dz = 0)."""
     D = q.shape[1] // Hq
     G = Hq // Hkv
     qb, qe = check_q_range(q_range, T, causal, p)
     check_sink(sink, q, Hq, causal, p)
+    check_softcap(softcap, causal, p, sink)
     Tq = qe - qb
-    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds, qb, qe)
+    s = _attn_probs(q, k, B, T, Hq, Hkv, D, scale, causal, window, bounds, qb, qe, softcap)
     pr = torch.exp(s - lse.view(B, Hq, Tq)[..., None])
     keep = _attn_keep(B, Hq, T, p, seed, site, q.device)
     z = torch.ones_like(pr) if keep is None else keep.to(pr.dtype) / (1.0 - p)   # fp64 inputs stay fp64
@@ -451,6 +476,8 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, s
     dvh = torch.matmul(pd.transpose(-1, -2), doh)                     # [B,Hq,T,D]
     dp = torch.matmul(doh, vh.transpose(-1, -2))
     ds = pr * (dp * z - delta)
+    if softcap:         # through the cap: 1 - tanh^2 from the capped scores (masked entries: ds = 0 already)
+        ds = ds * (1.0 - torch.where(torch.isfinite(s), s / softcap, torch.zeros_like(s)) ** 2)
     dqh = torch.matmul(ds, kh) * scale
     dkh = torch.matmul(ds.transpose(-1, -2), qh) * scale
     if G > 1:

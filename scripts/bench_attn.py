@@ -7,6 +7,7 @@
     python scripts/bench_attn.py --cp 8 --cp-layout zigzag [--window 4096]   # every rank's query ranges vs the whole row
     python scripts/bench_attn.py --q-range 0:2048 --q-range 30720:32768 --seq-lens 32768
     python scripts/bench_attn.py --sinks --seq-lens 4096,16384 [--out profiles/attention_sinks.txt]
+    python scripts/bench_attn.py --softcap 50 --seq-lens 4096,16384 --rounds 7 [--out profiles/attention_softcap.txt]
 
 Prints one line per kernel: time per call and TFLOP/s (causal FLOPs counted over the visible
 half).  Shapes: TinyGPT-A (B1 T2048 H16 D64, dropout 0.1, non-causal) and Mistral-7B
@@ -28,6 +29,11 @@ rank's summed time and the max / mean ratio over the ranks: the balance of the a
 (``attn_fwd(..., sink=)``: the SINK instantiation against its sink-less twin) at each ``--seq-lens`` length, full
 causal and with ``--sinks-window`` (default 4096), alternating in one process as above, plus the sink-gradient kernel
 ``attn_sink_bwd``.  The yardstick is the sink-less call of the same run; ``--out`` also writes the lines to a file.
+
+``--softcap C`` times forward, dQ and dK/dV of the Mistral-7B attention shape with logit soft-capping at cap C (the CAP
+instantiations) against the plain instantiations at each ``--seq-lens`` length, full causal and with
+``--sinks-window``, the six calls alternating in one process over ``--rounds`` rounds; each pass is reported on its
+own with the plain call's min .. max spread beside the ratio.
 """
 import argparse
 import json
@@ -263,6 +269,51 @@ def run_sinks(T, W, iters, rounds, B=1, Hq=32, Hkv=8, D=128, emit=print):
                 inside_spread=inside, dsink_us=med["dsink"])
 
 
+def run_softcap(T, W, cap, iters, rounds, B=1, Hq=32, Hkv=8, D=128, emit=print):
+    """Forward, dQ and dK/dV (window ``W``, 0 = full causal) without and with soft-capping at ``cap``, the six calls
+    alternating over ``rounds`` rounds after a warm-up round.  Each backward pass runs on its own forward's o / lse."""
+    C = ext()
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    qkv = torch.randn(B * T, (Hq + 2 * Hkv) * D, device=dev, dtype=torch.bfloat16, generator=g)
+    q, k, v = qkv[:, :Hq * D], qkv[:, Hq * D:(Hq + Hkv) * D], qkv[:, (Hq + Hkv) * D:]
+    do = torch.randn(B * T, Hq * D, device=dev, dtype=torch.bfloat16, generator=g)
+    dqkv = torch.empty_like(qkv)
+    dq, dk, dv = dqkv[:, :Hq * D], dqkv[:, Hq * D:(Hq + Hkv) * D], dqkv[:, (Hq + Hkv) * D:]
+    scale = D ** -0.5
+    fns = {}
+    for kind, kw in (("plain", {}), ("cap", {"softcap": cap})):
+        o, lse = C.attn_fwd(q, k, v, None, B, T, Hq, Hkv, scale, True, 0.0, window=W, **kw)
+        delta = C.attn_bwd_delta(o, do, B, T, Hq)
+
+        def fwd(kw=kw):
+            return C.attn_fwd(q, k, v, None, B, T, Hq, Hkv, scale, True, 0.0, window=W, **kw)
+
+        def dq_(kw=kw, o=o, lse=lse, delta=delta):
+            return C.attn_bwd_part(1, q, k, v, do, lse, delta, None, dq, None, B, T, Hq, Hkv, scale, True, 0.0, o,
+                                   window=W, **kw)
+
+        def dkdv(kw=kw, lse=lse, delta=delta):
+            return C.attn_bwd_part(0, q, k, v, do, lse, delta, None, dk, dv, B, T, Hq, Hkv, scale, True, 0.0, None,
+                                   window=W, **kw)
+        fns[("fwd", kind)], fns[("dq", kind)], fns[("dkdv", kind)] = fwd, dq_, dkdv
+    times = {key: [] for key in fns}
+    for r in range(rounds + 1):                 # round 0 warms up; the plain and the capped calls alternate
+        for key, fn in fns.items():
+            us = timeit(fn, iters)
+            if r:
+                times[key].append(us)
+    out = {}
+    for name in ("fwd", "dq", "dkdv"):
+        tp, tc = times[(name, "plain")], times[(name, "cap")]
+        mp, mc = sorted(tp)[len(tp) // 2], sorted(tc)[len(tc) // 2]
+        emit(f"T {T:6d} W {W:5d} cap {cap:g} {name:5s} plain {mp:9.1f} us ({min(tp):.1f} .. {max(tp):.1f})  "
+             f"capped {mc:9.1f} us ({min(tc):.1f} .. {max(tc):.1f})  ratio {mc / mp:.4f}  "
+             f"plain spread {min(tp) / mp:.4f} .. {max(tp) / mp:.4f}")
+        out[name] = dict(plain_us=mp, cap_us=mc, ratio=mc / mp, plain_min=min(tp), plain_max=max(tp))
+    return out
+
+
 def doc_tile_counts(bounds, T):
     """tile_counts for document bounds [2, 1, T] (CPU): the tile ranges of the bounds kernels."""
     lo, hi = bounds[0, 0].tolist(), bounds[1, 0].tolist()
@@ -343,9 +394,29 @@ def main():
     ap.add_argument("--sinks", action="store_true",
                     help="time the causal forward with and without attention sinks, and the sink-gradient kernel")
     ap.add_argument("--sinks-window", type=int, default=4096, help="the windowed variant of the --sinks comparison")
-    ap.add_argument("--out", default=None, help="--sinks: also write the result lines to this file")
+    ap.add_argument("--out", default=None, help="--sinks / --softcap: also write the result lines to this file")
+    ap.add_argument("--softcap", type=float, default=0.0,
+                    help="time forward, dQ and dK/dV with logit soft-capping at this cap against the plain kernels")
     a = ap.parse_args()
-    if a.sinks:
+    if a.softcap > 0:
+        lines = [f"# scripts/bench_attn.py --softcap {a.softcap:g}: forward, dQ and dK/dV of the M7B head shape (B1 Hq32 "
+                 "Hkv8 D128, bf16), the soft-capped (CAP) against the plain",
+                 f"# instantiation, medians of {a.rounds} interleaved rounds of {a.iters} calls in one process (min .. "
+                 "max in brackets); ratio = capped / plain; the yardstick is the",
+                 "# plain call of the same run, its own min .. max spread beside each ratio.  W = sliding window "
+                 "(0 = full causal).  One MI355X."]
+
+        def emit(line):
+            print(line, flush=True)
+            lines.append(line)
+        out = {}
+        for T in (int(x) for x in a.seq_lens.split(",")):
+            for W in (0, a.sinks_window):
+                out[f"T{T}_W{W}"] = run_softcap(T, W, a.softcap, a.iters, a.rounds, emit=emit)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+    elif a.sinks:
         lines = ["# scripts/bench_attn.py --sinks: the causal forward of the M7B head shape (B1 Hq32 Hkv8 D128, bf16) "
                  "without and with learned attention sinks,",
                  f"# medians of {a.rounds} interleaved rounds of {a.iters} calls in one process (min .. max in "
