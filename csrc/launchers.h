@@ -97,6 +97,14 @@ void dltb_xent_lse(const void* logits, const int64_t* targets, float* loss, floa
                    int64_t ignore_index, hipStream_t st);
 void dltb_xent_bwd_lse(void* logits, const int64_t* targets, const float* lse, int N, int V,
                        int64_t ignore_index, hipStream_t st);
+// the three with the head-loss options: c = softcap tanh(z / softcap) in place of z (softcap > 0; 0 = off) and the
+// z-loss z_coef lse^2 (kernels of their own: the three above keep their code objects)
+void dltb_xent_fwd_bwd_opt(void* logits, const int64_t* targets, float* loss, int N, int V,
+                           int64_t ignore_index, float softcap, float z_coef, hipStream_t st);
+void dltb_xent_lse_opt(const void* logits, const int64_t* targets, float* loss, float* lse, int N, int V,
+                       int64_t ignore_index, float softcap, float z_coef, hipStream_t st);
+void dltb_xent_bwd_lse_opt(void* logits, const int64_t* targets, const float* lse, int N, int V,
+                           int64_t ignore_index, float softcap, float z_coef, hipStream_t st);
 
 // adamw.hip
 int dltb_adamw_chunk();

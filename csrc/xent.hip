@@ -222,6 +222,184 @@ __global__ __launch_bounds__(1024) void xent_mean_kernel(const float* __restrict
   }
 }
 
+// ---------------------------------------------------------------- head-loss options: final-logit cap, z-loss
+// The three kernels above with two options (models/mistral.py, final_softcap / lm_z_loss_coef); they keep their
+// text, so their code objects do not change, and the option-taking variants are kernels of their own:
+//   c_j  = CAP ? cap tanh(z_j / cap) : z_j           fp32 in registers, never rounded to 16 bits
+//   lse  = logsumexp_j c_j
+//   loss = lse - c_t + zc lse^2
+//   dz_j = (softmax(c)_j (1 + 2 zc lse) - [j == t]) (1 - tanh(z_j / cap)^2)       (last factor 1 without CAP)
+// tanh in the form of the attention CAP kernels: e = exp2(2 log2(e) z / cap), r = rcp(1 + e), t = 1 - 2 r; r is
+// exactly 0 / 1 and t exactly +-1 when exp2 overflows / underflows, so 1 - t^2 and dz are exactly 0 there.
+// CAP is a compile-time switch and zc a runtime float: with zc == 0 the factor 1 + 2 zc lse is exactly 1.0f and
+// zc lse^2 exactly 0 (one multiply / one fma, no bits).
+// The fused kernel keeps ONE fp32 array per thread.  Without CAP it is xent_kernel's e = exp(z - m_t).  With CAP it
+// is t (the output needs 1 - t^2, and c = cap t): the exponential of the sum pass is not kept but formed again in
+// the output pass as exp(cap t - lse), one more v_exp per element instead of 64 more live registers at VPT = 8.
+constexpr float kXeLog2e = 1.4426950408889634f;
+
+DLTB_DEV float xent_tanh(float z, float capc) {     // capc = 2 log2(e) / cap
+  return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(z * capc)), 1.f);
+}
+
+// The per-thread pass of a row, shared by the fused and the read-only kernel statement for statement (with
+// xent_merge it makes their loss rows equal bit for bit): the thread's max m_t of c and its sum of exp(c - m_t).
+// a[j][k] is left as exp(z - m_t) without CAP (xent_kernel's e) and as tanh(z / cap) with it.
+template <int VPT, bool CAP>
+DLTB_DEV void xent_thread_pass(const bf16_t* z, int nvec, float cap, float capc, float (&a)[VPT][8], float& mt,
+                               float& st) {
+  mt = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) {
+    const int i = j * 512 + threadIdx.x;
+    if (i < nvec) {
+      unpack8(ld16<uint4>(z + i * 8), a[j]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (CAP) {
+          a[j][k] = xent_tanh(a[j][k], capc);
+          mt = fmaxf(mt, cap * a[j][k]);
+        } else {
+          mt = fmaxf(mt, a[j][k]);
+        }
+      }
+    }
+  }
+  st = 0.f;
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) {
+    const int i = j * 512 + threadIdx.x;
+    if (i < nvec) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (CAP) {
+          st += __expf(__builtin_fmaf(cap, a[j][k], -mt));      // explicit fma: the same in both kernels
+        } else {
+          a[j][k] = __expf(a[j][k] - mt);
+          st += a[j][k];
+        }
+      }
+    }
+  }
+}
+
+// loss row from the merged (M, S) and the target's c: lse - c_t + zc lse^2 in one fma (lse - c_t exactly when zc == 0)
+DLTB_DEV float xent_loss_row(float lse, float ct, float zc) { return __builtin_fmaf(zc * lse, lse, lse - ct); }
+
+template <int VPT, bool CAP>
+__global__ __launch_bounds__(512) void xent_opt_kernel(bf16_t* __restrict__ logits,
+                                                      const int64_t* __restrict__ targets,
+                                                      float* __restrict__ loss, int V, int64_t ignore_index,
+                                                      float cap, float zc) {
+  __shared__ float red[8], red2[8];
+  __shared__ float s_tlogit;
+  const int row = blockIdx.x;
+  bf16_t* z = logits + (long)row * V;
+  const int64_t t = targets[row];
+  const bool valid = (t != ignore_index) && t >= 0 && t < V;
+  const float capc = CAP ? 2.f * kXeLog2e / cap : 0.f;
+  if (threadIdx.x == 0) {
+    const float zt = valid ? bf2f(z[t]) : 0.f;
+    s_tlogit = CAP ? cap * xent_tanh(zt, capc) : zt;
+  }
+  const int nvec = V >> 3;
+  float a[VPT][8];
+  float mt, st;
+  xent_thread_pass<VPT, CAP>(z, nvec, cap, capc, a, mt, st);
+  float M, S;
+  xent_merge(mt, st, red, red2, M, S);
+  const float lse = M + __logf(S);
+  if (threadIdx.x == 0) loss[row] = valid ? xent_loss_row(lse, s_tlogit, zc) : 0.f;
+  const float kz = __builtin_fmaf(2.f * zc, lse, 1.f);                  // d(lse + zc lse^2) / d lse
+  const float scale = (mt == -INFINITY ? 0.f : __expf(mt - M) / S) * kz;  // without CAP: xent_kernel's scale
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) {
+    const int i = j * 512 + threadIdx.x;
+    if (i < nvec) {
+      float f[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        float p = 0.f;
+        if (valid) {
+          p = CAP ? __expf(__builtin_fmaf(cap, a[j][k], -lse)) * kz : a[j][k] * scale;
+          if (i * 8 + k == t) p -= 1.f;
+          if (CAP) p *= __builtin_fmaf(-a[j][k], a[j][k], 1.f);
+        }
+        f[k] = p;
+      }
+      *reinterpret_cast<uint4*>(z + i * 8) = pack8(f);
+    }
+  }
+}
+
+// xent_lse_kernel with the options: xent_opt_kernel's thread pass and merge, so its loss rows; lse is that of c.
+template <int VPT, bool CAP>
+__global__ __launch_bounds__(512) void xent_lse_opt_kernel(const bf16_t* __restrict__ logits,
+                                                          const int64_t* __restrict__ targets,
+                                                          float* __restrict__ loss, float* __restrict__ lse_out,
+                                                          int V, int64_t ignore_index, float cap, float zc) {
+  __shared__ float red[8], red2[8];
+  __shared__ float s_tlogit;
+  const int row = blockIdx.x;
+  const bf16_t* z = logits + (long)row * V;
+  const int64_t t = targets[row];
+  const bool valid = (t != ignore_index) && t >= 0 && t < V;
+  const float capc = CAP ? 2.f * kXeLog2e / cap : 0.f;
+  if (threadIdx.x == 0) {
+    const float zt = valid ? bf2f(z[t]) : 0.f;
+    s_tlogit = CAP ? cap * xent_tanh(zt, capc) : zt;
+  }
+  const int nvec = V >> 3;
+  float a[VPT][8];
+  float mt, st;
+  xent_thread_pass<VPT, CAP>(z, nvec, cap, capc, a, mt, st);
+  float M, S;
+  xent_merge(mt, st, red, red2, M, S);
+  const float lse = M + __logf(S);
+  if (threadIdx.x == 0) {
+    loss[row] = valid ? xent_loss_row(lse, s_tlogit, zc) : 0.f;
+    lse_out[row] = lse;
+  }
+}
+
+// xent_bwd_lse_kernel with the options (same grid over the chunk's vectors): from the kept lse of c,
+//   z[r][j] <- (exp(c_j - lse[r]) (1 + 2 zc lse[r]) - (j == t_r)) (1 - tanh(z_j / cap)^2)
+template <bool CAP>
+__global__ __launch_bounds__(256) void xent_bwd_lse_opt_kernel(bf16_t* __restrict__ logits,
+                                                              const int64_t* __restrict__ targets,
+                                                              const float* __restrict__ lse, int N, int V,
+                                                              int64_t ignore_index, float cap, float zc) {
+  const uint32_t nvec = (uint32_t)V >> 3;
+  const long base = (long)blockIdx.x * 256;
+  const long row0 = base / nvec;
+  const uint32_t c = (uint32_t)(base - row0 * nvec) + threadIdx.x;      // < nvec + 256
+  const uint32_t q = c / nvec;
+  const long row = row0 + q;
+  if (row >= N) return;
+  const int col = (int)(c - q * nvec) * 8;
+  bf16_t* p = logits + row * V + col;
+  const int64_t t = targets[row];
+  const bool valid = (t != ignore_index) && t >= 0 && t < V;
+  float f[8];
+  if (valid) {
+    const float l = lse[row];
+    const float kz = __builtin_fmaf(2.f * zc, l, 1.f);
+    const float capc = CAP ? 2.f * kXeLog2e / cap : 0.f;
+    unpack8(ld16<uint4>(p), f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float th = CAP ? xent_tanh(f[k], capc) : 0.f;
+      float g = __expf(CAP ? __builtin_fmaf(cap, th, -l) : f[k] - l) * kz - (col + k == t ? 1.f : 0.f);
+      if (CAP) g *= __builtin_fmaf(-th, th, 1.f);
+      f[k] = g;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = 0.f;
+  }
+  *reinterpret_cast<uint4*>(p) = pack8(f);
+}
+
 }  // namespace
 
 void dltb_xent_mean(const float* loss, const int64_t* targets, int N, int64_t ignore_index, float* out,
@@ -264,4 +442,60 @@ void dltb_xent_bwd_lse(void* logits, const int64_t* targets, const float* lse, i
   const long blocks = ((long)N * (V / 8) + 255) / 256;
   hipLaunchKernelGGL(xent_bwd_lse_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (bf16_t*)logits, targets,
                      lse, N, V, ignore_index);
+}
+
+// the option-taking variants: softcap > 0 selects the CAP instantiations, z_coef is a runtime operand
+void dltb_xent_fwd_bwd_opt(void* logits, const int64_t* targets, float* loss, int N, int V,
+                           int64_t ignore_index, float softcap, float z_coef, hipStream_t st) {
+  const int vpt = cdiv(V / 8, 512);
+#define DLTB_XE(K, C)                                                                                   \
+  hipLaunchKernelGGL((xent_opt_kernel<K, C>), dim3(N), dim3(512), 0, st, (bf16_t*)logits, targets, loss, \
+                     V, ignore_index, softcap, z_coef)
+#define DLTB_XEV(C)               \
+  if (vpt <= 1) DLTB_XE(1, C);      \
+  else if (vpt <= 2) DLTB_XE(2, C); \
+  else if (vpt <= 4) DLTB_XE(4, C); \
+  else if (vpt <= 8) DLTB_XE(8, C); \
+  else if (vpt <= 16) DLTB_XE(16, C); \
+  else DLTB_XE(32, C)
+  if (softcap > 0.f) {
+    DLTB_XEV(true);
+  } else {
+    DLTB_XEV(false);
+  }
+#undef DLTB_XEV
+#undef DLTB_XE
+}
+
+void dltb_xent_lse_opt(const void* logits, const int64_t* targets, float* loss, float* lse, int N, int V,
+                       int64_t ignore_index, float softcap, float z_coef, hipStream_t st) {
+  const int vpt = cdiv(V / 8, 512);
+#define DLTB_XL(K, C)                                                                                         \
+  hipLaunchKernelGGL((xent_lse_opt_kernel<K, C>), dim3(N), dim3(512), 0, st, (const bf16_t*)logits, targets, \
+                     loss, lse, V, ignore_index, softcap, z_coef)
+#define DLTB_XLV(C)               \
+  if (vpt <= 1) DLTB_XL(1, C);      \
+  else if (vpt <= 2) DLTB_XL(2, C); \
+  else if (vpt <= 4) DLTB_XL(4, C); \
+  else if (vpt <= 8) DLTB_XL(8, C); \
+  else if (vpt <= 16) DLTB_XL(16, C); \
+  else DLTB_XL(32, C)
+  if (softcap > 0.f) {
+    DLTB_XLV(true);
+  } else {
+    DLTB_XLV(false);
+  }
+#undef DLTB_XLV
+#undef DLTB_XL
+}
+
+void dltb_xent_bwd_lse_opt(void* logits, const int64_t* targets, const float* lse, int N, int V,
+                           int64_t ignore_index, float softcap, float z_coef, hipStream_t st) {
+  const long blocks = ((long)N * (V / 8) + 255) / 256;
+  if (softcap > 0.f)
+    hipLaunchKernelGGL(xent_bwd_lse_opt_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, (bf16_t*)logits,
+                       targets, lse, N, V, ignore_index, softcap, z_coef);
+  else
+    hipLaunchKernelGGL(xent_bwd_lse_opt_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, (bf16_t*)logits,
+                       targets, lse, N, V, ignore_index, softcap, z_coef);
 }

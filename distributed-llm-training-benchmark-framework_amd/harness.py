@@ -16,7 +16,7 @@ Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
 --doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk, --moe-experts, --moe-top-k,
 --moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef, --moe-dropless, --qk-norm,
---attn-sinks, --attn-softcap.
+--attn-sinks, --attn-softcap, --final-softcap, --lm-z-loss-coef.
 """
 import argparse
 import json
@@ -116,6 +116,14 @@ def build_parser():
                    help="causal tiers: attention logit soft-capping, every score x becomes C * tanh(x / C) before the "
                         "softmax (Gemma-2 uses 50), in capped instantiations of the three attention kernels; not "
                         "together with --attn-sinks; default: 0 = off")
+    p.add_argument("--final-softcap", type=float, default=0.0, metavar="C",
+                   help="causal tiers: final-logit soft-capping, the LM-head loss is formed from C * tanh(logits / C) "
+                        "(Gemma-2 / Gemma-3 use 30), in capped instantiations of the three loss kernels; default: "
+                        "0 = off")
+    p.add_argument("--lm-z-loss-coef", type=float, default=0.0, metavar="B",
+                   help="causal tiers: add B times the mean over the valid rows of logsumexp(logits)^2 to the LM-head "
+                        "loss (PaLM / OLMo-2 / Chameleon use about 1e-4), inside the loss kernels; the reported loss "
+                        "is the total; default: 0 = off")
     p.add_argument("--synthetic", action="store_true", help="accepted for compatibility (data is always synthetic)")
     # training
     p.add_argument("--steps", type=int, required=True)
@@ -274,6 +282,36 @@ def check_attn_softcap(cap, sinks, mcfg, tier):
     mcfg.validate()
 
 
+def check_final_softcap(cap, mcfg, tier):
+    """ValueError when ``--final-softcap`` is not a finite number >= 0 or is set for a tier without the untied causal
+    head; sets it on ``mcfg``."""
+    cap = float(cap or 0.0)
+    if cap == 0.0:
+        return
+    if not math.isfinite(cap) or cap < 0:
+        raise ValueError(f"--final-softcap must be a finite number >= 0 (0 = off), got {cap}")
+    if not mcfg.causal:
+        raise ValueError(f"--final-softcap needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the "
+                         "reference's plain softmax cross-entropy on its tied head")
+    mcfg.final_softcap = cap
+    mcfg.validate()
+
+
+def check_lm_z_loss(coef, mcfg, tier):
+    """ValueError when ``--lm-z-loss-coef`` is not a finite number >= 0 or is set for a tier without the untied causal
+    head; sets it on ``mcfg``."""
+    coef = float(coef or 0.0)
+    if coef == 0.0:
+        return
+    if not math.isfinite(coef) or coef < 0:
+        raise ValueError(f"--lm-z-loss-coef must be a finite number >= 0 (0 = off), got {coef}")
+    if not mcfg.causal:
+        raise ValueError(f"--lm-z-loss-coef needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the "
+                         "reference's plain softmax cross-entropy on its tied head")
+    mcfg.lm_z_loss_coef = coef
+    mcfg.validate()
+
+
 def check_moe(experts, top_k, factor, recompute, mcfg, tier, aux_coef=None, z_coef=None, dropless=False):
     """ValueError when the ``--moe-*`` flags are set for a tier without the routed FFN or together with
     ``--activation-recompute``, or ``--moe-dropless`` together with an explicit ``--moe-capacity-factor``; sets them
@@ -388,6 +426,8 @@ def train(args):
         check_attn_sinks(bool(getattr(args, "attn_sinks", False)), mcfg, args.tier)
         check_attn_softcap(getattr(args, "attn_softcap", 0.0), bool(getattr(args, "attn_sinks", False)), mcfg,
                            args.tier)
+        check_final_softcap(getattr(args, "final_softcap", 0.0), mcfg, args.tier)
+        check_lm_z_loss(getattr(args, "lm_z_loss_coef", 0.0), mcfg, args.tier)
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -424,6 +464,12 @@ def train(args):
         if mcfg.attn_softcap and is_main:
             print(f"attention soft-capping: scores capped to {mcfg.attn_softcap:g} * tanh(x / {mcfg.attn_softcap:g})",
                   flush=True)
+        if mcfg.final_softcap and is_main:
+            print(f"final-logit soft-capping: the loss is formed from {mcfg.final_softcap:g} * tanh(logits / "
+                  f"{mcfg.final_softcap:g})", flush=True)
+        if mcfg.lm_z_loss_coef and is_main:
+            print(f"LM-head z-loss: {mcfg.lm_z_loss_coef:g} * mean(logsumexp(logits)^2) over the valid rows, included "
+                  "in the reported loss", flush=True)
         cp = None
         if cp_n > 1:
             cp = _context.ContextParallel(cp_n, cp_layout, mcfg.sliding_window, world, rank)
@@ -582,6 +628,8 @@ def train(args):
             "head_chunk": head_chunk, "head_chunks": n_head_chunks,
             "attn_sinks": bool(mcfg.attn_sinks),
             "attn_softcap": float(mcfg.attn_softcap),
+            "final_softcap": float(mcfg.final_softcap),
+            "lm_z_loss_coef": float(mcfg.lm_z_loss_coef),
             # the last micro-step's assignments per layer and expert (before drops) and, with an auxiliary router
             # loss on, its per-layer values, read once, here
             "moe": model.moe_stats(head_rows) if mcfg.n_experts else None,
@@ -682,6 +730,8 @@ def main(argv=None):
         check_qk_norm(args.qk_norm, get_model_config(args.tier, args.seq_len), args.tier)
         check_attn_sinks(args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
         check_attn_softcap(args.attn_softcap, args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
+        check_final_softcap(args.final_softcap, get_model_config(args.tier, args.seq_len), args.tier)
+        check_lm_z_loss(args.lm_z_loss_coef, get_model_config(args.tier, args.seq_len), args.tier)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

@@ -66,6 +66,12 @@ class ModelConfig:
     # before the masks and the softmax (Gemma-2 / Gemma-3 / Grok-1; Gemma-2 uses 50); 0 = off.  No parameter; the CAP
     # instantiations of the three attention kernels (csrc/attention.hip).  Not together with attn_sinks.
     attn_softcap: float = 0.0
+    # final-logit soft-capping (mistral arch): the LM-head loss is formed from cap * tanh(logits / cap) (Gemma-2 /
+    # Gemma-3 use 30); 0 = off.  No parameter; the CAP instantiations of the three loss kernels (csrc/xent.hip).
+    final_softcap: float = 0.0
+    # z-loss on the LM head (mistral arch; PaLM, OLMo-2, Chameleon use about 1e-4): the loss gains
+    # lm_z_loss_coef * mean over the valid rows of logsumexp(logits)^2 (of the capped logits under final_softcap); 0 = off
+    lm_z_loss_coef: float = 0.0
 
     def __post_init__(self):
         self.validate()
@@ -103,6 +109,12 @@ class ModelConfig:
                              f"{self.arch!r}")
         if c > 0 and self.attn_sinks:
             raise ValueError("attn_softcap together with attn_sinks is not supported")
+        for name, what in (("final_softcap", "final-logit soft-capping"), ("lm_z_loss_coef", "LM-head z-loss")):
+            c = getattr(self, name)
+            if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c < 0:
+                raise ValueError(f"{name} must be a finite number >= 0 (0 = off), got {c!r}")
+            if c > 0 and self.arch != "mistral":
+                raise ValueError(f"{name} ({what}) needs the mistral arch, got arch {self.arch!r}")
         k, cf = self.moe_top_k, self.moe_capacity_factor
         if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4):
             raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
@@ -185,8 +197,8 @@ class ModelConfig:
         the T^2 / 2 (or window) count.  Without it the result is exactly the formula above.  With ``n_experts`` the
         FFN term counts ``moe_top_k`` experts and the router product per token.  ``qk_norm`` changes nothing here: it
         adds no matrix product (its 2 * head_dim weights per layer are elementwise), like the other norms; nor does
-        ``attn_sinks`` (one more softmax term per query row and head) or ``attn_softcap`` (elementwise on the
-        scores)."""
+        ``attn_sinks`` (one more softmax term per query row and head), ``attn_softcap`` (elementwise on the
+        scores) or ``final_softcap`` / ``lm_z_loss_coef`` (elementwise on the logits, inside the loss kernels)."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d

@@ -39,6 +39,12 @@ With ``cfg.attn_softcap`` = cap > 0 every attention score x becomes ``cap * tanh
 softmax (``attn_fwd`` / ``attn_bwd(..., softcap=)``: the CAP kernels of csrc/attention.hip) on every attention path --
 the whole row, the context-parallel ranges and both recompute modes.  It adds no parameter and keeps nothing more for
 the backward: lse is that of the capped scores and the backward kernels recompute the tanh.
+
+With ``cfg.final_softcap`` = C > 0 the head's loss is formed from ``c = C * tanh(logits / C)`` and with
+``cfg.lm_z_loss_coef`` = B > 0 it gains ``B * logsumexp(c)^2`` per valid row (``xent_fwd_bwd_`` / ``xent_lse`` /
+``xent_bwd_lse_(..., softcap=, z_coef=)``: the option kernels of csrc/xent.hip), unchunked and under ``head_chunk``.
+c exists in fp32 registers only; the row mean, the 1 / count scale and what the backward keeps are unchanged (the
+kept lse is that of c).  The logits handed back to a caller are the capped ones, rounded to the model's format.
 """
 import math
 
@@ -624,6 +630,23 @@ def head_chunks(rows, n):
     return 1 if n is None or n >= rows else -(-rows // n)
 
 
+def _head_loss_opts(cfg):
+    """The loss kernels' options of ``cfg.final_softcap`` / ``cfg.lm_z_loss_coef``; none when both are off, so the
+    calls (and their launches) are those of a config without the fields."""
+    if cfg.final_softcap or cfg.lm_z_loss_coef:
+        return {"softcap": float(cfg.final_softcap), "z_coef": float(cfg.lm_z_loss_coef)}
+    return {}
+
+
+def _capped_logits(logits, cap, copy):
+    """The logits a caller gets back (``return_logits`` / no targets; off the training path): under
+    ``final_softcap`` = cap the capped ones, ``cap * tanh(z / cap)`` formed in fp32 and rounded to the model's
+    format.  The loss is never formed from these: the kernels cap the raw product themselves, in registers."""
+    if cap:
+        return (cap * torch.tanh(logits.float() / cap)).to(logits.dtype)
+    return logits.clone() if copy else logits
+
+
 def _head_forward_chunked(ctx, x, model, targets, n):
     """:meth:`_HeadFn.forward` under ``model.head_chunk = n < rows``: the logits exist one [n, V] chunk at a time
     (each chunk's block returns to the allocator before the next product asks for it) and only their loss and
@@ -638,7 +661,7 @@ def _head_forward_chunked(ctx, x, model, targets, n):
     for r0 in range(0, R, n):
         r1 = min(r0 + n, R)
         logits = F_.linear_fwd(h[r0:r1], w_head)
-        F_.xent_lse(logits, tg[r0:r1], -1, loss_rows[r0:r1], lse[r0:r1])
+        F_.xent_lse(logits, tg[r0:r1], -1, loss_rows[r0:r1], lse[r0:r1], **_head_loss_opts(model.cfg))
         del logits
     lc = F_.xent_mean(loss_rows, tg, -1)          # (mean, count) over all rows, as unchunked
     loss, count = lc[0], lc[1:2]
@@ -668,7 +691,7 @@ def _head_backward_chunked(ctx, dloss):
     for r0 in range(0, R, n):
         r1 = min(r0 + n, R)
         dl = F_.linear_fwd(h[r0:r1], w_head)
-        F_.xent_bwd_lse_(dl, tg[r0:r1], lse[r0:r1], -1)
+        F_.xent_bwd_lse_(dl, tg[r0:r1], lse[r0:r1], -1, **_head_loss_opts(model.cfg))
         F_.linear_wgrad(dl, hs[r0:r1], dwh, None, acc_h if r0 == 0 else True)
         dh[r0:r1].copy_(F_.head_dgrad(dl, w_head, wt, g))
         del dl
@@ -694,12 +717,13 @@ class _HeadFn(torch.autograd.Function):
         logits = F_.linear_fwd(h, w_head)
         if targets is None:
             rt.release_forward(unit)
+            logits = _capped_logits(logits, model.cfg.final_softcap, False)
             ctx.mark_non_differentiable(logits)
             ctx.no_loss = True
             return logits, logits.new_zeros(())
-        kept = logits.clone() if return_logits else None
+        kept = _capped_logits(logits, model.cfg.final_softcap, True) if return_logits else None
         tg = targets.reshape(-1)
-        loss_rows = F_.xent_fwd_bwd_(logits, tg, -1)
+        loss_rows = F_.xent_fwd_bwd_(logits, tg, -1, **_head_loss_opts(model.cfg))
         lc = F_.xent_mean(loss_rows, tg, -1)          # (mean, count) on the device
         loss, count = lc[0], lc[1:2]
         rt.release_forward(unit)

@@ -211,9 +211,15 @@ class OracleMistral(nn.Module):
             g, u = gu.chunk(2, -1)
             x = x + layer.mlp.down_proj(F.silu(g) * u)
         logits = self.lm_head(self.model.norm(x))
+        if cfg.final_softcap:       # final-logit soft-capping: the loss and the returned logits are the capped ones
+            logits = cfg.final_softcap * torch.tanh(logits / cfg.final_softcap)
         loss = None
         if targets is not None:
             loss = F.cross_entropy(logits.view(-1, logits.size(-1)), targets.view(-1), ignore_index=-1)
+            if cfg.lm_z_loss_coef:  # z-loss: mean over the valid rows of logsumexp(logits)^2
+                tg = targets.view(-1)
+                z2 = torch.logsumexp(logits.view(-1, logits.size(-1)), -1).pow(2)
+                loss = loss + cfg.lm_z_loss_coef * (z2 * (tg != -1)).sum() / (tg != -1).sum().clamp(min=1)
             for term in aux:
                 loss = loss + term
         return logits, loss

@@ -539,29 +539,45 @@ def embed_bwd(dx, idx, dwte, dwpe, accumulate_wpe, p, seed, site):
         ref.embed_bwd(dx, idx, dwte, dwpe, accumulate_wpe, p, seed, site)
 
 
-def xent_fwd_bwd_(logits2d, targets1d, ignore_index=-1):
+def xent_fwd_bwd_(logits2d, targets1d, ignore_index=-1, softcap=0.0, z_coef=0.0):
+    """Loss rows (fp32) of the logits, which are overwritten with their unscaled gradient.  ``softcap`` = C /
+    ``z_coef`` = B (:func:`ref.check_xent_opts`; 0 = off): the loss of ``c = C tanh(z / C)`` plus ``B lse(c)^2`` and
+    its gradient through the cap (the option kernels of csrc/xent.hip); with both 0 the call is today's."""
+    ref.check_xent_opts(softcap, z_coef)
     if _gpu(logits2d):
+        if softcap or z_coef:
+            return ext().xent_fwd_bwd_opt_(logits2d, targets1d, ignore_index, float(softcap), float(z_coef))
         return ext().xent_fwd_bwd_(logits2d, targets1d, ignore_index)
-    return ref.xent_fwd_bwd_(logits2d, targets1d, ignore_index)
+    return ref.xent_fwd_bwd_(logits2d, targets1d, ignore_index, softcap, z_coef)
 
 
-def xent_lse(logits2d, targets1d, ignore_index=-1, loss_out=None, lse_out=None):
+def xent_lse(logits2d, targets1d, ignore_index=-1, loss_out=None, lse_out=None, softcap=0.0, z_coef=0.0):
     """(loss rows, log-sum-exp rows) in fp32 of a logits chunk that is only read (the chunked head's forward);
-    the loss rows are :func:`xent_fwd_bwd_`'s bit for bit.  ``loss_out`` / ``lse_out``: contiguous f32 [N]
-    slices of the caller's whole-batch rows."""
+    the loss rows are :func:`xent_fwd_bwd_`'s bit for bit, at the same ``softcap`` / ``z_coef`` too (the log-sum-exp
+    is then that of the capped logits).  ``loss_out`` / ``lse_out``: contiguous f32 [N] slices of the caller's
+    whole-batch rows."""
+    ref.check_xent_opts(softcap, z_coef)
     if _gpu(logits2d):
-        loss, lse = ext().xent_lse(logits2d, targets1d, ignore_index, loss_out, lse_out)
+        if softcap or z_coef:
+            loss, lse = ext().xent_lse_opt(logits2d, targets1d, ignore_index, float(softcap), float(z_coef),
+                                           loss_out, lse_out)
+        else:
+            loss, lse = ext().xent_lse(logits2d, targets1d, ignore_index, loss_out, lse_out)
         return loss, lse
-    loss, lse = ref.xent_lse(logits2d, targets1d, ignore_index)
+    loss, lse = ref.xent_lse(logits2d, targets1d, ignore_index, softcap, z_coef)
     return _into(loss_out, loss), _into(lse_out, lse)
 
 
-def xent_bwd_lse_(logits2d, targets1d, lse, ignore_index=-1):
+def xent_bwd_lse_(logits2d, targets1d, lse, ignore_index=-1, softcap=0.0, z_coef=0.0):
     """logits <- exp(logits - lse) - onehot(targets) in place (0 for ignored rows): the chunked head's
-    backward on its recomputed logits."""
+    backward on its recomputed logits; with the forward's ``softcap`` / ``z_coef``, :func:`xent_fwd_bwd_`'s gradient
+    under them."""
+    ref.check_xent_opts(softcap, z_coef)
     if _gpu(logits2d):
+        if softcap or z_coef:
+            return ext().xent_bwd_lse_opt_(logits2d, targets1d, lse, ignore_index, float(softcap), float(z_coef))
         return ext().xent_bwd_lse_(logits2d, targets1d, lse, ignore_index)
-    return ref.xent_bwd_lse_(logits2d, targets1d, lse, ignore_index)
+    return ref.xent_bwd_lse_(logits2d, targets1d, lse, ignore_index, softcap, z_coef)
 
 
 def xent_mean(loss_rows, targets1d, ignore_index=-1):

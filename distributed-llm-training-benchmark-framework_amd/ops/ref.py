@@ -234,40 +234,76 @@ def embed_bwd(dx, idx, dwte, dwpe, accumulate_wpe, p, seed, site):
 
 
 # ------------------------------------------------------------------------------ xent
-def xent_fwd_bwd_(logits, targets, ignore_index):
-    """Returns per-row loss; overwrites logits with unscaled (softmax - onehot)."""
+def check_xent_opts(softcap, z_coef):
+    """The head-loss options: ``softcap`` = C (the loss is formed from ``C * tanh(z / C)``) and ``z_coef`` = B (the
+    loss gains ``B * logsumexp^2``); both finite numbers >= 0, 0 = off."""
+    for name, v in (("softcap", softcap), ("z_coef", z_coef)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"xent: {name} must be a finite number >= 0 (0 = off), got {v!r}")
+
+
+def _xent_capped(logits, softcap):
+    """(c, 1 - tanh^2) in fp32: ``c = softcap * tanh(z / softcap)`` and the cap's derivative; (z, None) when off."""
     z = _f(logits)
+    if not softcap:
+        return z, None
+    t = torch.tanh(z / softcap)
+    return softcap * t, 1.0 - t * t
+
+
+def _xent_grad(pr, dcap, t, valid, lse, z_coef):
+    """``(pr (1 + 2 B lse) - onehot) (1 - tanh^2)``, 0 for ignored rows."""
+    if z_coef:
+        pr = pr * (1.0 + 2.0 * z_coef * lse)[:, None]
+    pr.scatter_add_(-1, t[:, None], -torch.ones_like(pr[:, :1]))
+    if dcap is not None:
+        pr = pr * dcap
+    return torch.where(valid[:, None], pr, torch.zeros_like(pr))
+
+
+def xent_fwd_bwd_(logits, targets, ignore_index, softcap=0.0, z_coef=0.0):
+    """Returns per-row loss; overwrites logits with unscaled (softmax - onehot).  With ``softcap`` = C / ``z_coef`` =
+    B (:func:`check_xent_opts`): c = C tanh(z / C), ``loss = lse(c) - c_t + B lse^2`` and
+    ``dz = (softmax(c) (1 + 2 B lse) - onehot) (1 - (c / C)^2)``."""
+    check_xent_opts(softcap, z_coef)
+    z, dcap = _xent_capped(logits, softcap)
     valid = targets != ignore_index
     lse = torch.logsumexp(z, -1)
     t = targets.clamp(min=0)
     tl = z.gather(-1, t[:, None])[:, 0]
-    loss = torch.where(valid, lse - tl, torch.zeros_like(lse))
-    pr = torch.softmax(z, -1)
-    pr.scatter_add_(-1, t[:, None], -torch.ones_like(tl)[:, None])
-    pr = torch.where(valid[:, None], pr, torch.zeros_like(pr))
+    row = lse - tl
+    if z_coef:
+        row = row + z_coef * lse * lse
+    loss = torch.where(valid, row, torch.zeros_like(lse))
+    pr = _xent_grad(torch.softmax(z, -1), dcap, t, valid, lse, z_coef)
     logits.copy_(pr.to(logits.dtype))
     return loss
 
 
-def xent_lse(logits, targets, ignore_index):
+def xent_lse(logits, targets, ignore_index, softcap=0.0, z_coef=0.0):
     """(per-row loss, per-row log-sum-exp) in fp32; the logits are only read.  The loss is
-    :func:`xent_fwd_bwd_`'s, the same expressions on the same values."""
-    z = _f(logits)
+    :func:`xent_fwd_bwd_`'s, the same expressions on the same values; under ``softcap`` the log-sum-exp is that of
+    the capped logits."""
+    check_xent_opts(softcap, z_coef)
+    z, _ = _xent_capped(logits, softcap)
     valid = targets != ignore_index
     lse = torch.logsumexp(z, -1)
     tl = z.gather(-1, targets.clamp(min=0)[:, None])[:, 0]
-    return torch.where(valid, lse - tl, torch.zeros_like(lse)), lse
+    row = lse - tl
+    if z_coef:
+        row = row + z_coef * lse * lse
+    return torch.where(valid, row, torch.zeros_like(lse)), lse
 
 
-def xent_bwd_lse_(logits, targets, lse, ignore_index):
+def xent_bwd_lse_(logits, targets, lse, ignore_index, softcap=0.0, z_coef=0.0):
     """Overwrites logits with unscaled ``exp(z - lse) - onehot`` (0 for ignored rows) from the kept
-    log-sum-exp: :func:`xent_fwd_bwd_`'s gradient without its reduction.  Returns logits."""
-    z = _f(logits)
+    log-sum-exp: :func:`xent_fwd_bwd_`'s gradient without its reduction, options included.  Returns logits."""
+    check_xent_opts(softcap, z_coef)
+    z, dcap = _xent_capped(logits, softcap)
     valid = targets != ignore_index
     t = targets.clamp(min=0)
-    pr = torch.exp(z - lse.to(torch.float32)[:, None])
-    pr.scatter_add_(-1, t[:, None], -torch.ones_like(pr[:, :1]))
-    pr = torch.where(valid[:, None], pr, torch.zeros_like(pr))
+    l = lse.to(torch.float32)
+    pr = _xent_grad(torch.exp(z - l[:, None]), dcap, t, valid, l, z_coef)
     logits.copy_(pr.to(logits.dtype))
     return logits
 

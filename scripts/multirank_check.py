@@ -25,7 +25,7 @@ ranks (dltb/parallel/context.py): the ranks of a group read the same rows, and t
 world-1 run trains.  Its Mistral-shape cases (``CP_CASES``: every strategy, a sliding window, packed documents)
 are not part of the default ``--cases``.  ``--activation-recompute`` sets the Mistral-shape cases' saved set; a run
 with it must train the model the ``off`` run trains; so must one with ``--head-chunk N`` (the Mistral-shape cases' LM
-head in chunks of N rows).  ``--qk-norm`` turns QK-norm on in the Mistral-shape cases, ``--attn-sinks`` the learned attention sinks, ``--attn-softcap C`` the attention logit soft-capping.  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
+head in chunks of N rows).  ``--qk-norm`` turns QK-norm on in the Mistral-shape cases, ``--attn-sinks`` the learned attention sinks, ``--attn-softcap C`` the attention logit soft-capping, ``--final-softcap C`` / ``--lm-z-loss-coef B`` the head-loss options.  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
 DeepSpeed ZeRO-2/3 wrap) -- at any world size the trained model must be the one the global batch
 defines.
 """
@@ -115,6 +115,8 @@ def run_case(name, spec, world, rank, device, a):
         mcfg.attn_sinks = True
     if a.attn_softcap and mcfg.arch == "mistral":                 # the Mistral-shape cases only
         mcfg.attn_softcap = a.attn_softcap
+    if mcfg.arch == "mistral":                                    # the Mistral-shape cases only
+        mcfg.final_softcap, mcfg.lm_z_loss_coef = a.final_softcap, a.lm_z_loss_coef
     mcfg.validate()
     with torch.device(device):
         model = build_model(mcfg)
@@ -206,6 +208,10 @@ def main():
                     help="learned attention sinks in the Mistral-shape cases (models/mistral.py)")
     ap.add_argument("--attn-softcap", type=float, default=0.0,
                     help="attention logit soft-capping in the Mistral-shape cases (models/mistral.py); 0 = off")
+    ap.add_argument("--final-softcap", type=float, default=0.0,
+                    help="final-logit soft-capping in the Mistral-shape cases (models/mistral.py); 0 = off")
+    ap.add_argument("--lm-z-loss-coef", type=float, default=0.0,
+                    help="LM-head z-loss coefficient in the Mistral-shape cases (models/mistral.py); 0 = off")
     a = ap.parse_args()
     from dltb.utils.dist import cleanup_distributed, setup_distributed
     world = int(os.environ.get("WORLD_SIZE", "1"))
