@@ -158,6 +158,200 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_kernel(
   }
 }
 
+// ------------------------------------------------------------------ block-scaled FP8 moments
+// exp_avg and sqrt(exp_avg_sq) as OCP E4M3 codes (one byte each) with one fp32 power-of-two scale per 256
+// consecutive elements of a table row: with the W = 4 layout a quantisation block is one wavefront in one
+// iteration, so its absmax is a wave reduction.  The contract (scale rule, stochastic rounding on the fp32 bit
+// pattern, the floor of the second moment) is mirrored bit for bit by ops/ref.py (fp8_quantize / adamw_flat_fp8).
+constexpr int kFp8Block = 256;
+constexpr int kFp8RowBlocks = kAdamChunk / kFp8Block;
+constexpr float kFp8MinNormal = 0.015625f;       // 2^-6: below it E4M3 is a fixed-point grid of 2^-9
+constexpr float kFp8MinSub = 0.001953125f;       // 2^-9
+
+// exponent e of the block scale 2^e: 0 for an all-zero block, else the smallest e >= -126 with a * 2^-e <= 448
+// (448 = 1.75 * 2^8: a mantissa above 1.75 needs one more)
+DLTB_DEV int fp8_scale_exp(float a) {
+  const int e = (int)((__float_as_uint(a) + 0x1FFFFFu) >> 23) - 135;
+  return a == 0.f ? 0 : (e < -126 ? -126 : e);
+}
+DLTB_DEV float fp8_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+
+// per-launch keys of the two moments (kind 0: exp_avg, 1: sqrt(exp_avg_sq)) and the word of one element
+DLTB_DEV uint32_t fp8_key(uint64_t seed, uint32_t counter, uint32_t kind) {
+  return fmix32(fmix32(counter * DLTB_C_ROW + (uint32_t)(seed >> 32)) ^ ((uint32_t)seed + (kind + 1u) * DLTB_C_COL));
+}
+DLTB_DEV uint32_t fp8_rand20(uint32_t key, int64_t idx) {
+  const uint32_t x = (uint32_t)idx * DLTB_C_COL + (uint32_t)((uint64_t)idx >> 32) * DLTB_C_ROW;
+  return fmix32(key ^ x) >> 12;
+}
+
+// y * inv rounded to one of its two E4M3 neighbours: the random word r20 (20 bits; 0x80000 rounds to nearest)
+// is added to the fp32 bit pattern and the low 20 mantissa bits are cleared, which leaves E4M3's 3.  Below 2^-6
+// the value is first moved into the binade [2^-6, 2^-5), whose 3-bit grid is the subnormal grid 2^-9.  The
+// result is exactly representable, so the conversion instruction does not round again.  floor_pos: a positive y
+// never becomes 0 (second moment).
+DLTB_DEV float fp8_round(float y, float inv, uint32_t r20, bool floor_pos) {
+#pragma clang fp contract(off)
+  const float t = fabsf(y) * inv;
+  const bool sub = t < kFp8MinNormal;
+  const float w = sub ? t + kFp8MinNormal : t;
+  float q = __uint_as_float((__float_as_uint(w) + r20) & 0xFFF00000u);
+  if (sub) q -= kFp8MinNormal;
+  if (floor_pos && y > 0.f && q == 0.f) q = kFp8MinSub;
+  return q == 0.f ? 0.f : copysignf(q, y);
+}
+DLTB_DEV uint32_t fp8_pack4(const float* q) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], w, true);
+  return (uint32_t)w;
+}
+DLTB_DEV void fp8_unpack4(uint32_t w, float scale, float* f) {
+  f[0] = __builtin_amdgcn_cvt_f32_fp8((int)w, 0) * scale;
+  f[1] = __builtin_amdgcn_cvt_f32_fp8((int)w, 1) * scale;
+  f[2] = __builtin_amdgcn_cvt_f32_fp8((int)w, 2) * scale;
+  f[3] = __builtin_amdgcn_cvt_f32_fp8((int)w, 3) * scale;
+}
+// this lane's four values y (owner indices idx .. idx + 3; zeros in a lane past the end) of a block that is the
+// whole wave -> four codes and (every lane) the block's scale
+DLTB_DEV uint32_t fp8_quant_wave(const float* y, int64_t idx, uint32_t key, bool nearest, bool floor_pos,
+                                 float* scale_out) {
+  const float a = wave_max(fmaxf(fmaxf(fabsf(y[0]), fabsf(y[1])), fmaxf(fabsf(y[2]), fabsf(y[3]))));
+  const int e = fp8_scale_exp(a);
+  const float inv = fp8_pow2(-e);
+  float q[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    q[k] = fp8_round(y[k], inv, nearest ? 0x80000u : fp8_rand20(key, idx + k), floor_pos);
+  *scale_out = fp8_pow2(e);
+  return fp8_pack4(q);
+}
+
+template <typename G, int T = kAdamThreads>
+DLTB_DEV void adamw_fp8_block(float* __restrict__ master, uint32_t* __restrict__ mq, uint32_t* __restrict__ sq,
+                              float* __restrict__ mscale, float* __restrict__ sscale,
+                              const G* __restrict__ grad, bf16_t* __restrict__ dst, int64_t start, int64_t seg_end,
+                              int64_t dst_base, const AdamHp& h, uint32_t key_m, uint32_t key_s) {
+  constexpr int W = 4;
+  constexpr int ITERS = kAdamChunk / (T * W);
+  static_assert(T / 64 * ITERS == kFp8RowBlocks && 64 * W == kFp8Block, "one wave and iteration per block");
+  const int wave = threadIdx.x >> 6;
+  v4f P[ITERS];
+  uint32_t MC[ITERS], SC[ITERS];
+  float MS[ITERS], SS[ITERS];
+  float Gr[ITERS][W];
+#pragma unroll
+  for (int it = 0; it < ITERS; ++it) {
+    const int64_t i = start + ((int64_t)it * T + threadIdx.x) * W;
+    if (i < seg_end) {
+      P[it] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(master + i));
+      MC[it] = __builtin_nontemporal_load(mq + (i >> 2));
+      SC[it] = __builtin_nontemporal_load(sq + (i >> 2));
+      MS[it] = mscale[it * (T / 64) + wave];
+      SS[it] = sscale[it * (T / 64) + wave];
+      load4<G>(grad + i, Gr[it]);
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < ITERS; ++it) {
+    const int64_t off = ((int64_t)it * T + threadIdx.x) * W;
+    const int64_t i = start + off;
+    // the block (this wave, this iteration) lies past the segment: so do the later ones (wave-uniform)
+    if (start + ((int64_t)it * T + wave * 64) * W >= seg_end) break;
+    const bool live = i < seg_end;
+    float p[W] = {0.f, 0.f, 0.f, 0.f}, m[W] = {0.f, 0.f, 0.f, 0.f}, s[W] = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+      float d[W];
+      fp8_unpack4(MC[it], MS[it], m);
+      fp8_unpack4(SC[it], SS[it], d);
+#pragma unroll
+      for (int e = 0; e < W; ++e) {
+        p[e] = P[it][e];
+        float v = d[e] * d[e];
+        adam_elem(p[e], m[e], v, Gr[it][e], h);
+        s[e] = sqrtf(v);
+      }
+    }
+    float ms, ss;
+    const uint32_t mc = fp8_quant_wave(m, i, key_m, false, false, &ms);
+    const uint32_t sc = fp8_quant_wave(s, i, key_s, false, true, &ss);
+    if (live) {
+      __builtin_nontemporal_store((v4f){p[0], p[1], p[2], p[3]}, reinterpret_cast<v4f*>(master + i));
+      __builtin_nontemporal_store(mc, mq + (i >> 2));
+      __builtin_nontemporal_store(sc, sq + (i >> 2));
+      uint2 o;
+      o.x = pack_bf2(p[0], p[1]);
+      o.y = pack_bf2(p[2], p[3]);
+      *reinterpret_cast<uint2*>(dst + dst_base + off) = o;
+      if ((threadIdx.x & 63) == 0) {       // the block's first lane is live whenever the block is
+        mscale[it * (T / 64) + wave] = ms;
+        sscale[it * (T / 64) + wave] = ss;
+      }
+    }
+  }
+}
+
+// adamw_kernel with one-byte moments: the same tables and W = 4 streaming layout; row_off is the global table
+// row of blk_seg[0] (a launch over a slice of the tables addresses the scales of the global row).  hp[4] holds
+// the launch counter as integer bits.
+template <typename G>
+__global__ __launch_bounds__(kAdamThreads) void adamw_fp8_kernel(
+    float* __restrict__ master, uint32_t* __restrict__ mq, uint32_t* __restrict__ sq,
+    float* __restrict__ mscale, float* __restrict__ sscale,
+    const G* __restrict__ grad, const int* __restrict__ blk_seg, const int64_t* __restrict__ blk_start,
+    const int64_t* __restrict__ seg_ostart, const int64_t* __restrict__ seg_len,
+    const int64_t* __restrict__ seg_dst, const float* __restrict__ gscale, const float* __restrict__ hp,
+    float lr, float beta1, float beta2, float eps, float wd, float step_size, float inv_sqrt_bc2, int nblk,
+    int64_t row_off, uint64_t seed, uint32_t counter) {
+  if (hp) {
+    if (hp[3] != 0.f) return;   // skipped step: codes, scales and master stay
+    lr = hp[0];
+    step_size = hp[1];
+    inv_sqrt_bc2 = hp[2];
+    counter = __float_as_uint(hp[4]);
+  }
+  const uint32_t key_m = fp8_key(seed, counter, 0u), key_s = fp8_key(seed, counter, 1u);
+  for (int bi = blockIdx.x; bi < nblk; bi += gridDim.x) {
+    const int seg = blk_seg[bi];
+    const int64_t start = blk_start[bi];
+    const int64_t s0 = seg_ostart[seg];
+    const int64_t seg_end = s0 + seg_len[seg];
+    DLTB_DCHECK(seg >= 0 && start >= s0 && start < seg_end);
+    bf16_t* dst = reinterpret_cast<bf16_t*>(seg_dst[seg]);
+    const AdamHp h{lr, beta1, beta2, eps, wd, step_size, inv_sqrt_bc2, gscale ? *gscale : 1.f};
+    const int64_t row = row_off + bi;
+    adamw_fp8_block<G>(master, mq, sq, mscale + row * kFp8RowBlocks, sscale + row * kFp8RowBlocks, grad, dst,
+                       start, seg_end, start - s0, h, key_m, key_s);
+  }
+}
+
+// the quantiser and the decoder alone, on a flat tensor whose blocks start at its first element (one segment's
+// rows): element j belongs to scale j / 256 and has the owner index owner_off + j
+__global__ __launch_bounds__(kAdamThreads) void fp8_quant_kernel(
+    const float* __restrict__ x, uint32_t* __restrict__ codes, float* __restrict__ scales, int64_t n,
+    int64_t nblocks, int kind, bool nearest, uint64_t seed, uint32_t counter, int64_t owner_off) {
+  const uint32_t key = fp8_key(seed, counter, (uint32_t)kind);
+  const int lane = threadIdx.x & 63;
+  for (int64_t b = (int64_t)blockIdx.x * (kAdamThreads / 64) + (threadIdx.x >> 6); b < nblocks;
+       b += (int64_t)gridDim.x * (kAdamThreads / 64)) {
+    const int64_t j = b * kFp8Block + lane * 4;
+    float y[4] = {0.f, 0.f, 0.f, 0.f};
+    if (j < n) load4<float>(x + j, y);
+    float sc;
+    const uint32_t c = fp8_quant_wave(y, owner_off + j, key, nearest, kind == 1, &sc);
+    if (j < n) codes[j >> 2] = c;
+    if (lane == 0) scales[b] = sc;
+  }
+}
+
+__global__ __launch_bounds__(kAdamThreads) void fp8_dequant_kernel(
+    const uint32_t* __restrict__ codes, const float* __restrict__ scales, float* __restrict__ out, int64_t n4) {
+  for (int64_t j = (int64_t)blockIdx.x * kAdamThreads + threadIdx.x; j < n4; j += (int64_t)gridDim.x * kAdamThreads) {
+    float f[4];
+    fp8_unpack4(codes[j], scales[j / (kFp8Block / 4)], f);
+    *reinterpret_cast<float4*>(out + 4 * j) = make_float4(f[0], f[1], f[2], f[3]);
+  }
+}
+
 // sum of squares in a FIXED order (bitwise reproducible: eager runs, graph replays and ranks agree):
 // a grid-stride pass writes one partial per block, a one-block pass adds them in index order.
 constexpr int kSumsqBlocks = 1024;
@@ -276,6 +470,46 @@ void dltb_adamw(float* master, float* exp_avg, float* exp_avg_sq, const void* gr
     hipLaunchKernelGGL(adamw_kernel<float>, dim3(grid), dim3(thr), 0, st, master,
                        exp_avg, exp_avg_sq, (const float*)grad, blk_seg, blk_start, seg_ostart,
                        seg_len, seg_dst, gscale, hp, lr, beta1, beta2, eps, wd, step_size, inv_sqrt_bc2, nblocks);
+}
+
+void dltb_adamw_fp8(float* master, uint8_t* mq, uint8_t* sq, float* mscale, float* sscale, const void* grad,
+                    bool grad_bf16, const int* blk_seg, const int64_t* blk_start, int nblocks,
+                    const int64_t* seg_ostart, const int64_t* seg_len, const int64_t* seg_dst,
+                    const float* gscale, const float* hp, float lr, float beta1, float beta2, float eps, float wd,
+                    float step_size, float inv_sqrt_bc2, int grid_cap, int64_t row_off, uint64_t seed,
+                    uint32_t counter, hipStream_t st) {
+  if (nblocks <= 0) return;
+  const int grid = grid_cap > 0 && grid_cap < nblocks ? grid_cap : nblocks;
+  const int thr = kAdamThreads;
+  uint32_t* mq4 = reinterpret_cast<uint32_t*>(mq);
+  uint32_t* sq4 = reinterpret_cast<uint32_t*>(sq);
+  if (grad_bf16)
+    hipLaunchKernelGGL(adamw_fp8_kernel<bf16_t>, dim3(grid), dim3(thr), 0, st, master, mq4, sq4, mscale, sscale,
+                       (const bf16_t*)grad, blk_seg, blk_start, seg_ostart, seg_len, seg_dst, gscale, hp, lr,
+                       beta1, beta2, eps, wd, step_size, inv_sqrt_bc2, nblocks, row_off, seed, counter);
+  else
+    hipLaunchKernelGGL(adamw_fp8_kernel<float>, dim3(grid), dim3(thr), 0, st, master, mq4, sq4, mscale, sscale,
+                       (const float*)grad, blk_seg, blk_start, seg_ostart, seg_len, seg_dst, gscale, hp, lr,
+                       beta1, beta2, eps, wd, step_size, inv_sqrt_bc2, nblocks, row_off, seed, counter);
+}
+
+void dltb_fp8_quant(const float* x, uint8_t* codes, float* scales, int64_t n, int kind, bool nearest,
+                    uint64_t seed, uint32_t counter, int64_t owner_off, hipStream_t st) {
+  if (n <= 0) return;
+  const int64_t nblocks = (n + kFp8Block - 1) / kFp8Block;
+  int64_t g = (nblocks + kAdamThreads / 64 - 1) / (kAdamThreads / 64);
+  if (g > 4096) g = 4096;
+  hipLaunchKernelGGL(fp8_quant_kernel, dim3((int)g), dim3(kAdamThreads), 0, st, x,
+                     reinterpret_cast<uint32_t*>(codes), scales, n, nblocks, kind, nearest, seed, counter, owner_off);
+}
+
+void dltb_fp8_dequant(const uint8_t* codes, const float* scales, float* out, int64_t n, hipStream_t st) {
+  if (n <= 0) return;
+  const int64_t n4 = n / 4;
+  int64_t g = (n4 + kAdamThreads - 1) / kAdamThreads;
+  if (g > 4096) g = 4096;
+  hipLaunchKernelGGL(fp8_dequant_kernel, dim3((int)g), dim3(kAdamThreads), 0, st,
+                     reinterpret_cast<const uint32_t*>(codes), scales, out, n4);
 }
 
 int dltb_sumsq_partials() { return kSumsqBlocks; }

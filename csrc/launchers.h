@@ -113,6 +113,18 @@ void dltb_adamw(float* master, float* exp_avg, float* exp_avg_sq, const void* gr
                 const int64_t* seg_len, const int64_t* seg_dst, const float* gscale, const float* hp,
                 float lr, float beta1, float beta2, float eps, float wd, float step_size,
                 float inv_sqrt_bc2, int grid_cap, hipStream_t st);   // grid_cap 0: one block per row
+// block-scaled FP8 moments: E4M3 codes + one fp32 scale per 256 elements of a table row ([rows, 16]); row_off is
+// the global table row of blk_seg[0]; counter is read from hp[4] (integer bits) where hp is given
+void dltb_adamw_fp8(float* master, uint8_t* mq, uint8_t* sq, float* mscale, float* sscale, const void* grad,
+                    bool grad_bf16, const int* blk_seg, const int64_t* blk_start, int nblocks,
+                    const int64_t* seg_ostart, const int64_t* seg_len, const int64_t* seg_dst,
+                    const float* gscale, const float* hp, float lr, float beta1, float beta2, float eps, float wd,
+                    float step_size, float inv_sqrt_bc2, int grid_cap, int64_t row_off, uint64_t seed,
+                    uint32_t counter, hipStream_t st);
+// the quantiser / decoder of the kernel above on a flat tensor (blocks from its first element); kind 0: m, 1: s
+void dltb_fp8_quant(const float* x, uint8_t* codes, float* scales, int64_t n, int kind, bool nearest,
+                    uint64_t seed, uint32_t counter, int64_t owner_off, hipStream_t st);
+void dltb_fp8_dequant(const uint8_t* codes, const float* scales, float* out, int64_t n, hipStream_t st);
 int dltb_sumsq_partials();
 void dltb_sumsq(const void* x, bool bf16, long n, float* out, float* part, hipStream_t st);
 void dltb_clip_coef(const float* norm_sq, float max_norm, float* coef, float* norm_out,

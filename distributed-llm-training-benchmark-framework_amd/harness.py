@@ -143,6 +143,11 @@ def build_parser():
     p.add_argument("--grad-reduce", choices=["micro", "window"], default="micro",
                    help="ZeRO-2 gradient reduce-scatter every micro-step (DeepSpeed) or once per "
                         "accumulation window")
+    p.add_argument("--optimizer-state", choices=["fp32", "fp8"], default="fp32",
+                   help="AdamW moments: fp32, or fp8 = block-scaled OCP E4M3 codes (one byte per element for exp_avg "
+                        "and for sqrt(exp_avg_sq), one fp32 power-of-two scale per 256 elements, stochastic "
+                        "rounding): 6 bytes of optimizer state per parameter instead of 12; master weights stay "
+                        "fp32; every strategy and tier")
     p.add_argument("--grad-comm-dtype", choices=["auto", "bf16", "fp16", "fp32"], default="auto",
                    help="DDP gradient all-reduce dtype: the compute dtype or fp32; auto = fp32 when DDP "
                         "runs the reference's fp16 path (torch DDP reduces fp32 grads), else the compute dtype")
@@ -200,7 +205,8 @@ def _engine_for(args, model, device):
             fc = dict(fc or {}, sharding_strategy=args.fsdp_sharding)
     cfg = engine_config(args.strategy, args.grad_accum, args.accum_semantics, ds, fc,
                         compute_dtype=DTYPES[args.dtype], bucket_mb=args.bucket_mb, seed=args.seed,
-                        grad_reduce=getattr(args, "grad_reduce", "micro"))
+                        grad_reduce=getattr(args, "grad_reduce", "micro"),
+                        optimizer_state=getattr(args, "optimizer_state", "fp32"))
     cfg.extra["grad_comm_dtype"] = "fp32" if getattr(args, "grad_comm_dtype", None) == "fp32" else "compute"
     if args.strategy == "ddp" and getattr(args, "ddp_shard_optimizer", False):
         cfg.extra["shard_optimizer"] = True       # DDP + ZeroRedundancyOptimizer (parallel/replicated.py)
@@ -467,6 +473,9 @@ def train(args):
         if mcfg.final_softcap and is_main:
             print(f"final-logit soft-capping: the loss is formed from {mcfg.final_softcap:g} * tanh(logits / "
                   f"{mcfg.final_softcap:g})", flush=True)
+        if getattr(args, "optimizer_state", "fp32") == "fp8" and is_main:
+            print("optimizer state: AdamW moments as block-scaled FP8 (E4M3) codes, stochastically rounded; master "
+                  "weights fp32", flush=True)
         if mcfg.lm_z_loss_coef and is_main:
             print(f"LM-head z-loss: {mcfg.lm_z_loss_coef:g} * mean(logsumexp(logits)^2) over the valid rows, included "
                   "in the reported loss", flush=True)
@@ -630,6 +639,7 @@ def train(args):
             "attn_softcap": float(mcfg.attn_softcap),
             "final_softcap": float(mcfg.final_softcap),
             "lm_z_loss_coef": float(mcfg.lm_z_loss_coef),
+            "optimizer_state": engine.opt.state, "optimizer_bytes": engine.opt.state_bytes,
             # the last micro-step's assignments per layer and expert (before drops) and, with an auxiliary router
             # loss on, its per-layer values, read once, here
             "moe": model.moe_stats(head_rows) if mcfg.n_experts else None,

@@ -11,7 +11,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from .rng import attn_keep_mask, keep_mask, keep_mask_2d, site_seed
+from .rng import C_COL, C_ROW, MASK32, _fmix32, _mul32, attn_keep_mask, keep_mask, keep_mask_2d, site_seed
 
 
 def _f(t):
@@ -724,3 +724,99 @@ def adamw_flat(master, exp_avg, exp_avg_sq, grad, lr, beta1, beta2, eps, wd, ste
     exp_avg_sq.mul_(beta2).addcmul_(g, g, value=1.0 - beta2)
     denom = (exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(eps)
     master.addcdiv_(exp_avg, denom, value=-(lr / bc1))
+
+
+# ---- block-scaled FP8 moments (csrc/adamw.hip adamw_fp8_kernel; the contract, bit for bit) -------------------
+# exp_avg and s = sqrt(exp_avg_sq) are stored as OCP E4M3 codes (uint8, torch.float8_e4m3fn bit patterns) with one
+# fp32 power-of-two scale per 256 consecutive elements of a block-table row.  Rows are ADAM_CHUNK elements and start
+# at a segment's first element, so a segment's blocks start at its first element too.
+FP8_BLOCK = 256
+ADAM_CHUNK = 4096                 # csrc/adamw.hip kAdamChunk (ext().adamw_chunk())
+FP8_ROW_BLOCKS = ADAM_CHUNK // FP8_BLOCK
+FP8_MAX = 448.0
+FP8_NEAREST = 0x80000             # the random word that rounds to nearest (ties away from zero)
+FP8_KIND_M, FP8_KIND_S = 0, 1
+
+
+def fp8_scale_exp(a):
+    """Exponent e of a block's scale 2^e for its absmax ``a`` (fp32 tensor): 0 where a == 0, else the smallest
+    e >= -126 with a * 2^-e <= 448 (448 = 1.75 * 2^8, so a mantissa above 1.75 takes one more)."""
+    bits = a.contiguous().view(torch.int32).to(torch.int64) & MASK32
+    e = ((bits + 0x1FFFFF) >> 23) - 135
+    return torch.where(a == 0, torch.zeros_like(e), e.clamp(min=-126))
+
+
+def _pow2(e):
+    return ((e + 127) << 23).to(torch.int32).view(torch.float32)
+
+
+def fp8_key(seed: int, counter: int, kind: int) -> int:
+    """Per-launch key of one moment: fmix32(fmix32(counter * C_ROW + seed_hi) ^ (seed_lo + (kind + 1) * C_COL))."""
+    one = lambda v: int(_fmix32(torch.tensor(v & MASK32, dtype=torch.int64)))
+    return one(one((counter & MASK32) * C_ROW + ((seed >> 32) & MASK32)) ^ (((seed & MASK32) + (kind + 1) * C_COL) & MASK32))
+
+
+def fp8_rand20(seed: int, counter: int, kind: int, idx):
+    """The 20 random bits of the owner indices ``idx`` (int64 tensor)."""
+    x = (_mul32(idx & MASK32, C_COL) + _mul32((idx >> 32) & MASK32, C_ROW)) & MASK32
+    return _fmix32(x ^ fp8_key(seed, counter, kind)) >> 12
+
+
+def fp8_round(y, inv, r20, floor_pos):
+    """``y * inv`` (fp32; ``inv`` a power of two) rounded to one of its two E4M3 neighbours by the 20-bit words
+    ``r20`` (tensor or int): the word is added to the fp32 bit pattern and the low 20 mantissa bits are cleared.
+    Values below 2^-6 are first moved into [2^-6, 2^-5), whose 3-bit grid is E4M3's subnormal grid 2^-9.
+    ``floor_pos``: a positive y never becomes 0.  The result is exactly representable in E4M3."""
+    t = y.abs() * inv
+    sub = t < 2.0 ** -6
+    w = torch.where(sub, t + 2.0 ** -6, t)
+    bits = ((w.contiguous().view(torch.int32).to(torch.int64) & MASK32) + r20) & 0xFFF00000
+    bits = torch.where(bits >= 2 ** 31, bits - 2 ** 32, bits)          # NaN / inf patterns of a poisoned input
+    q = bits.to(torch.int32).view(torch.float32)
+    q = torch.where(sub, q - 2.0 ** -6, q)
+    if floor_pos:
+        q = torch.where((y > 0) & (q == 0), torch.full_like(q, 2.0 ** -9), q)
+    return torch.where(q == 0, torch.zeros_like(q), torch.copysign(q, y))
+
+
+def fp8_quantize(y, kind, seed, counter, owner_off=0, rounding="stochastic"):
+    """Flat fp32 ``y`` (blocks of 256 from its first element, the last one may be partial; element j has the owner
+    index ``owner_off + j``) -> (codes uint8 [n], scales fp32 [ceil(n / 256)])."""
+    assert rounding in ("stochastic", "nearest")
+    y = y.detach().float().reshape(-1)
+    n = y.numel()
+    nb = (n + FP8_BLOCK - 1) // FP8_BLOCK
+    yp = torch.zeros(nb * FP8_BLOCK, dtype=torch.float32, device=y.device)
+    yp[:n] = y
+    yp = yp.view(nb, FP8_BLOCK)
+    e = fp8_scale_exp(yp.abs().amax(dim=1))
+    if rounding == "nearest":
+        r20 = FP8_NEAREST
+    else:
+        idx = torch.arange(owner_off, owner_off + nb * FP8_BLOCK, dtype=torch.int64, device=y.device)
+        r20 = fp8_rand20(int(seed), int(counter), kind, idx).view(nb, FP8_BLOCK)
+    q = fp8_round(yp, _pow2(-e)[:, None], r20, kind == FP8_KIND_S)
+    codes = q.to(torch.float8_e4m3fn).view(torch.uint8).reshape(-1)[:n].clone()
+    return codes, _pow2(e)
+
+
+def fp8_dequantize(codes, scales):
+    """codes uint8 [n], scales fp32 [ceil(n / 256)] -> fp32 [n]: the E4M3 value times its block's scale (exact)."""
+    n = codes.numel()
+    v = codes.reshape(-1).view(torch.float8_e4m3fn).float()
+    return v * scales.repeat_interleave(FP8_BLOCK)[:n]
+
+
+def adamw_flat_fp8(master, mq, sq, mscale, sscale, grad, lr, beta1, beta2, eps, wd, step, gscale=None, seed=0,
+                   counter=0, owner_off=0, rounding="stochastic"):
+    """:func:`adamw_flat` on ONE segment's views with FP8 moments: ``mq`` / ``sq`` uint8 codes, ``mscale`` /
+    ``sscale`` the segment's ceil(len / 256) scales (views, updated in place).  v_old = (s_code * scale)^2; the
+    update runs in fp32 with this step's v_new in the denominator; m_new and sqrt(v_new) are stored."""
+    m = fp8_dequantize(mq, mscale)
+    d = fp8_dequantize(sq, sscale)
+    v = d * d
+    adamw_flat(master, m, v, grad, lr, beta1, beta2, eps, wd, step, gscale)
+    for kind, val, codes, scales in ((FP8_KIND_M, m, mq, mscale), (FP8_KIND_S, v.sqrt(), sq, sscale)):
+        c, sc = fp8_quantize(val, kind, seed, counter, owner_off, rounding)
+        codes.copy_(c)
+        scales.copy_(sc)

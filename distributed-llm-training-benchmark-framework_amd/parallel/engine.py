@@ -41,6 +41,8 @@ class EngineConfig:
     compute_dtype: torch.dtype = torch.bfloat16
     bucket_mb: float = 64.0                   # gradient bucket cap (xGMI-tuned default)
     seed: int = 42
+    # AdamW moments: "fp32", or "fp8" = block-scaled E4M3 codes with stochastic rounding (optim/adamw.py)
+    optimizer_state: str = "fp32"
     # sharded engines
     reshard_after_forward: bool = True
     prefetch: int = 1                         # units gathered ahead (forward and backward)

@@ -182,7 +182,8 @@ class ReplicatedEngine(Engine):
             opt_segs = [(bk.start, bk.end - bk.start, self.flat_param[bk.start:bk.end]) for bk in L.buckets]
             assert sum(x[1] for x in opt_segs) == g_full.numel() == L.total
         del master_full
-        self.opt = FlatAdamW(master, opt_segs, cfg.lr, cfg.betas, cfg.eps, cfg.weight_decay)
+        self.opt = FlatAdamW(master, opt_segs, cfg.lr, cfg.betas, cfg.eps, cfg.weight_decay,
+                             state=cfg.optimizer_state, seed=cfg.seed)
         self._ag_pending = {}    # bucket -> async all-gather of updated parameters (deferred step)
         self._defer_opt = (self.stage >= 1 and self.world > 1 and self._overlap and
                            bool(cfg.extra.get("defer_opt", os.environ.get("DLTB_DEFER_OPT", "1") == "1")))
@@ -620,7 +621,7 @@ class ReplicatedEngine(Engine):
     def memory_report(self):
         e = self.flat_param.element_size()
         return {"param_bytes": self.flat_param.numel() * e, "grad_bytes": self.flat_grad.numel() * e,
-                "optimizer_bytes": self.opt.state_bytes,
+                "optimizer_bytes": self.opt.state_bytes, "optimizer_state": self.opt.state,
                 "buckets": len(self.layout.buckets),
                 "bucket_mb": [round(b.numel * e / 2**20, 2) for b in self.layout.buckets]}
 

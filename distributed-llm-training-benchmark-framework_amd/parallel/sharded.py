@@ -155,7 +155,8 @@ class ShardedEngine(Engine):
         if owner > p_chunk:
             segs.append((p_chunk, owner - p_chunk, self.shard_buf))
         self.opt = FlatAdamW(master, segs, cfg.lr, cfg.betas, cfg.eps, cfg.weight_decay,
-                             sub_group=int(cfg.extra.get("sub_group_elems", 0)))
+                             sub_group=int(cfg.extra.get("sub_group_elems", 0)),
+                             state=cfg.optimizer_state, seed=cfg.seed)
         self.rs_out = torch.zeros(owner, dtype=dt, device=dev)
         self.acc = torch.zeros(owner, dtype=torch.float32, device=dev) if (self.accum > 1 and self.world > 1) else None
         total_sharded = sum(g.total for g in groups)
@@ -687,7 +688,7 @@ class ShardedEngine(Engine):
     def memory_report(self):
         e = self.shard_buf.element_size()
         return {"shard_param_bytes": self.shard_buf.numel() * e, "persistent_param_bytes": self.p_flat.numel() * e,
-                "optimizer_bytes": self.opt.state_bytes, "groups": len(self.groups),
+                "optimizer_bytes": self.opt.state_bytes, "optimizer_state": self.opt.state, "groups": len(self.groups),
                 "largest_group_mb": round(max(g.total for g in self.groups) * e / 2**20, 2),
                 "keep_all_gathered": self.keep_all,
                 # speed-for-HBM buffers beyond DeepSpeed / torch FSDP's footprint (models < 2B params,

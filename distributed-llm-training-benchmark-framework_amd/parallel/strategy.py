@@ -50,18 +50,22 @@ def load_fsdp_config(path: str) -> dict:
 def engine_config(strategy: str, grad_accum: int = 1, semantics: str = "reference",
                   ds_config: Optional[dict] = None, fsdp_config: Optional[dict] = None,
                   compute_dtype=torch.bfloat16, bucket_mb: float = 64.0, seed: int = 42,
-                  overrides: Optional[dict] = None, grad_reduce: str = "micro") -> EngineConfig:
+                  overrides: Optional[dict] = None, grad_reduce: str = "micro",
+                  optimizer_state: str = "fp32") -> EngineConfig:
     """``grad_reduce`` (ZeRO-2 only): ``micro`` reduce-scatters the gradients after every micro-step
     (DeepSpeed stage 2, configs/deepspeed/zero2.json); ``window`` accumulates them locally over the
     ``grad_accum`` window and reduce-scatters once, during the boundary micro-step's backward
     (ZeRO-1 communication: 1/grad_accum of the xGMI traffic).  Optimizer state stays sharded
     either way, and the engine's flat gradient buffer is full-size in both modes, so HBM is the
-    same."""
+    same.  ``optimizer_state``: ``fp32`` AdamW moments, or ``fp8`` (block-scaled E4M3 codes, optim/adamw.py)."""
+    if optimizer_state not in ("fp32", "fp8"):
+        raise ValueError(f"optimizer_state must be fp32 or fp8, not {optimizer_state}")
     if grad_reduce not in ("micro", "window"):
         raise ValueError(f"grad_reduce must be micro or window, not {grad_reduce}")
     if strategy not in STRATEGIES:
         raise ValueError(f"unknown strategy {strategy}")
-    cfg = EngineConfig(strategy=strategy, compute_dtype=compute_dtype, bucket_mb=bucket_mb, seed=seed)
+    cfg = EngineConfig(strategy=strategy, compute_dtype=compute_dtype, bucket_mb=bucket_mb, seed=seed,
+                       optimizer_state=optimizer_state)
     ds = ds_config or {}
     zero_like = strategy in ("zero2", "zero3") or semantics == "uniform"
     if zero_like:

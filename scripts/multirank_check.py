@@ -118,7 +118,7 @@ def run_case(name, spec, world, rank, device, a):
     if mcfg.arch == "mistral":                                    # the Mistral-shape cases only
         mcfg.final_softcap, mcfg.lm_z_loss_coef = a.final_softcap, a.lm_z_loss_coef
     mcfg.validate()
-    with torch.device(device):
+    with torch.device(a.init_device or device):
         model = build_model(mcfg)
     cp = a.context_parallel
     if cp > 1:
@@ -139,7 +139,8 @@ def run_case(name, spec, world, rank, device, a):
             over["persistence_threshold"] = spec["persist"]
     over.update(spec.get("over", {}))
     cfg = engine_config(spec["strategy"], a.accum, "uniform", None, fc, bucket_mb=a.bucket_mb,
-                        overrides=over, grad_reduce=spec.get("grad_reduce", "micro"))
+                        overrides=over, grad_reduce=spec.get("grad_reduce", "micro"),
+                        optimizer_state=a.optimizer_state)
     cfg.extra["grad_comm_dtype"] = spec.get("grad_comm_dtype", "compute")
     cfg.extra.update(spec.get("extra", {}))
     eng = make_engine(model, cfg, device)
@@ -212,6 +213,11 @@ def main():
                     help="final-logit soft-capping in the Mistral-shape cases (models/mistral.py); 0 = off")
     ap.add_argument("--lm-z-loss-coef", type=float, default=0.0,
                     help="LM-head z-loss coefficient in the Mistral-shape cases (models/mistral.py); 0 = off")
+    ap.add_argument("--init-device", default=None,
+                    help="draw the initial parameters on this device (cpu: a GPU run starts from the CPU run's "
+                         "parameters); default: the run's device")
+    ap.add_argument("--optimizer-state", default="fp32", choices=["fp32", "fp8"],
+                    help="AdamW moments of every case: fp32, or block-scaled FP8 codes (optim/adamw.py)")
     a = ap.parse_args()
     from dltb.utils.dist import cleanup_distributed, setup_distributed
     world = int(os.environ.get("WORLD_SIZE", "1"))
