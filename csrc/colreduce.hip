@@ -29,6 +29,9 @@ struct ColPartArgs {
   const int64_t* seed_ptr;
 };
 
+// SUMS = false: the elementwise GELU / DROP work alone (the window-wide dW GEMM forms these bias gradients,
+// gemm_tn.hip COLSUM): no column accumulation, no LDS fold, no partial store.
+template <bool SUMS>
 __global__ __launch_bounds__(256) void colpart_kernel(ColPartArgs A) {
   __shared__ __attribute__((aligned(16))) float red[2][4][512];
   const DltbColPartSeg& S = A.seg[blockIdx.z];
@@ -41,6 +44,7 @@ __global__ __launch_bounds__(256) void colpart_kernel(ColPartArgs A) {
   const int r1 = min(S.N, r0 + rps);
   const int kind = S.kind;
   DLTB_DCHECK(k % 8 == 0 && kind >= 0 && kind <= 4 && r1 <= S.N);
+  DLTB_DCHECK(SUMS ? S.part != nullptr : (kind == DLTB_COLPART_GELU || kind == DLTB_COLPART_DROP));
   float a0[8], a1[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { a0[e] = 0.f; a1[e] = 0.f; }
@@ -58,7 +62,7 @@ __global__ __launch_bounds__(256) void colpart_kernel(ColPartArgs A) {
         for (int e = 0; e < 8; ++e) v[e] *= gelu_grad_c(fv[e]);
         const uint4 o = pack8(v);
         *reinterpret_cast<uint4*>(S.dst + off) = o;
-        unpack8(o, v);                                   // sum the rounded value the GEMM consumes
+        if (SUMS) unpack8(o, v);                         // sum the rounded value the GEMM consumes
       } else if (kind == DLTB_COLPART_DROP) {
         if (A.thr16) {
           const uint32_t rk = rng_row_key(seed, (uint32_t)r);
@@ -71,7 +75,7 @@ __global__ __launch_bounds__(256) void colpart_kernel(ColPartArgs A) {
         }
         const uint4 o = pack8(v);
         *reinterpret_cast<uint4*>(S.dst + off) = o;
-        unpack8(o, v);
+        if (SUMS) unpack8(o, v);
       } else if (kind == DLTB_COLPART_LN || kind == DLTB_COLPART_RMS) {
         float xv[8];
         unpack8(ld16<uint4>(S.b + off), xv);
@@ -83,10 +87,13 @@ __global__ __launch_bounds__(256) void colpart_kernel(ColPartArgs A) {
           v[e] *= (xv[e] - mean) * rstd;
         }
       }
+      if (SUMS) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) a0[e] += v[e];
+        for (int e = 0; e < 8; ++e) a0[e] += v[e];
+      }
     }
   }
+  if (!SUMS) return;
   const bool two = kind == DLTB_COLPART_LN;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -181,7 +188,7 @@ int dltb_colpart_partials(int N) {
 }
 
 void dltb_colpart(const DltbColPartSeg* segs, int nseg, int P, uint32_t thr16, float drop_scale,
-                  const int64_t* seed, hipStream_t st) {
+                  const int64_t* seed, bool sums, hipStream_t st) {
   ColPartArgs A{};
   int maxk = 0;
   for (int i = 0; i < nseg; ++i) {
@@ -192,7 +199,9 @@ void dltb_colpart(const DltbColPartSeg* segs, int nseg, int P, uint32_t thr16, f
   A.thr16 = thr16;
   A.drop_scale = drop_scale;
   A.seed_ptr = seed;
-  hipLaunchKernelGGL(colpart_kernel, dim3(cdiv(maxk, 512), P, nseg), dim3(256), 0, st, A);
+  const dim3 grid(cdiv(maxk, 512), P, nseg);
+  if (sums) hipLaunchKernelGGL(colpart_kernel<true>, grid, dim3(256), 0, st, A);
+  else hipLaunchKernelGGL(colpart_kernel<false>, grid, dim3(256), 0, st, A);
 }
 
 void dltb_colreduce_multi(const DltbColRedSeg* segs, int nseg, hipStream_t st) {

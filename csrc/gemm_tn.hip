@@ -38,6 +38,9 @@ struct TnArgs {
   long sa, sb, sc;                            // batch strides (elements)
   int M, N, K, batch;
   int accumulate;
+  bf16_t* colsum;                             // COLSUM kernels: colsum[b][m] (+)= sum_k A[b][k][m], else unused
+  long scs;                                   // its batch stride (elements)
+  int cs_accumulate;
 };
 
 typedef __attribute__((ext_vector_type(4))) float f4;
@@ -82,6 +85,17 @@ constexpr int kStage3 = 2 * kImg3;            // 32 KiB
 constexpr int kRing3 = 4;
 constexpr int kGlds3 = kImg3 / 1024 / 8;      // 2 per wave, operand and stage
 
+
+// COLSUM: the n-tile-0 workgroup of every m-tile also forms the column sums of its A (dY) tile -- a linear
+// layer's bias gradient, dY^T 1 -- from the fragments the loop holds anyway: one more MFMA per m-fragment
+// and k-step against an all-ones X fragment (every row of its 16 x 16 result is the fragment's column sum,
+// summed in fp32 in the MFMA's fixed k order).  The four n-waves of an m-half hold the same eight A
+// fragments, so wave wn takes two of them over ALL k-steps: two MFMAs on top of 32 per step, nothing to
+// combine across waves, no atomics.  To keep "which two" out of the loop, a COLSUM wave numbers its
+// m-fragments rotated by 2 wn (register set i holds fragment (i + 2 wn) & 7: only the LDS read offsets and
+// the epilogue's row addresses change), so every wave's two are its register sets 0 and 1; the loop gains one
+// workgroup-uniform branch per k-step.  Without COLSUM the rotation is the constant 0 and nothing changes.
+template <bool COLSUM>
 __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(TnArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -148,8 +162,10 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(TnArgs g) {
   const int hq = fq | ((fg & 1) << 2);
   const uint32_t rowoff = (uint32_t)((8 * fg + fq) * kRowB + 8 * fp);
   uint32_t offm[8], offn[4];
+  const int rot = COLSUM ? 2 * wn : 0;          // register set i <-> m-fragment fm(i) of the wave's 128 rows
+  auto fm = [&](int i) { return COLSUM ? ((i + rot) & 7) : i; };
 #pragma unroll
-  for (int i = 0; i < 8; ++i) offm[i] = rowoff + ((((wm * 128 + 16 * i) >> 4) ^ hq) << 5);
+  for (int i = 0; i < 8; ++i) offm[i] = rowoff + ((((wm * 128 + 16 * fm(i)) >> 4) ^ hq) << 5);
 #pragma unroll
   for (int j = 0; j < 4; ++j) offn[j] = kImg3 + rowoff + ((((wn * 64 + 16 * j) >> 4) ^ hq) << 5);
 
@@ -158,6 +174,11 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(TnArgs g) {
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  const bool cs = COLSUM && nb == 0;
+  f4 cacc[2] = {f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};   // COLSUM: of register sets 0 and 1
+  bfx8 ones;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ones[e] = (h16_t)1.0f;
 
   auto read_all = [&](int kt, bfx8 (&fa)[8], bfx8 (&fb)[4]) {
     const uint32_t base = lds0 + (kt & (kRing3 - 1)) * kStage3;
@@ -177,6 +198,10 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(TnArgs g) {
     for (int i = 0; i < 8; ++i) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(cb[j], ca[i], acc[i][j]);
+      if (COLSUM && i == 1 && cs) {
+        cacc[0] = mfma16(ones, ca[0], cacc[0]);
+        cacc[1] = mfma16(ones, ca[1], cacc[1]);
+      }
       __builtin_amdgcn_sched_barrier(0);
       if (i < 4) nb[i] = tn_frag<0>(nbase, offn[i]);
       na[i] = tn_frag<0>(nbase, offm[i]);
@@ -210,7 +235,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(TnArgs g) {
     uint2 o;
     o.x = pack_bf2(v[0], v[1]);
     o.y = pack_bf2(v[2], v[3]);
-    *reinterpret_cast<uint2*>(cbase + (long)(16 * i) * g.ldc + 16 * j) = o;
+    *reinterpret_cast<uint2*>(cbase + (long)(16 * fm(i)) * g.ldc + 16 * j) = o;
   };
   if (g.accumulate) {
     // every old value in flight at once (the fragment registers are dead here): one memory latency per tile
@@ -219,7 +244,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(TnArgs g) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) old[i][j] = *reinterpret_cast<const uint2*>(cbase + (long)(16 * i) * g.ldc + 16 * j);
+      for (int j = 0; j < 4; ++j)
+        old[i][j] = *reinterpret_cast<const uint2*>(cbase + (long)(16 * fm(i)) * g.ldc + 16 * j);
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -237,6 +263,18 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(TnArgs g) {
         store(i, j, v);
       }
   }
+  if (cs && lane < 16) {
+    // every row of a column-sum accumulator holds the same sums: lanes 0..15 store element 0 (m = lane);
+    // register sets 0 and 1 are fragments 2 wn and 2 wn + 1
+    bf16_t* sp = g.colsum + (long)bt * g.scs + m0 + wm * 128 + 16 * rot + lane;
+    DLTB_DCHECK(fm(1) == rot + 1 && m0 + wm * 128 + 16 * rot + 16 + lane < g.M);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float v = cacc[t][0];
+      if (g.cs_accumulate) v += bf2f(sp[16 * t]);
+      sp[16 * t] = f2bf(v);
+    }
+  }
 }
 
 }  // namespace
@@ -246,7 +284,8 @@ bool dltb_gemm_tn_supported(int M, int N, int K) {
 }
 
 int dltb_gemm_tn(const void* a, const void* b, void* c, long lda, long ldb, long ldc, long sa, long sb, long sc,
-                 int M, int N, int K, int batch, int accumulate, hipStream_t st) {
+                 int M, int N, int K, int batch, int accumulate, void* colsum, long scs, int cs_accumulate,
+                 hipStream_t st) {
   if (!dltb_gemm_tn_supported(M, N, K) || batch < 1) return -1;
   TnArgs g{};
   g.a = (const bf16_t*)a;
@@ -263,9 +302,17 @@ int dltb_gemm_tn(const void* a, const void* b, void* c, long lda, long ldb, long
   g.K = K;
   g.batch = batch;
   g.accumulate = accumulate;
+  g.colsum = (bf16_t*)colsum;
+  g.scs = scs;
+  g.cs_accumulate = cs_accumulate;
   constexpr int smem = kRing3 * kStage3;
-  allow_dynamic_lds<gemm_tn_kernel>(smem);
   const dim3 grid((unsigned)((long)(M / kTM) * (N / kTN) * batch));
-  hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(512), smem, st, g);
+  if (colsum) {
+    allow_dynamic_lds<gemm_tn_kernel<true>>(smem);
+    hipLaunchKernelGGL(gemm_tn_kernel<true>, grid, dim3(512), smem, st, g);
+  } else {
+    allow_dynamic_lds<gemm_tn_kernel<false>>(smem);
+    hipLaunchKernelGGL(gemm_tn_kernel<false>, grid, dim3(512), smem, st, g);
+  }
   return 0;
 }

@@ -35,7 +35,8 @@ int dltb_norm_bwd_fused_blocks(int N);
 bool dltb_norm_bwd_fused(const void* dy, const void* s, const void* w, const float* mean,
                          const float* rstd, const void* dres, void* dx, float* part, int N, int d,
                          bool rms, bool dxsum, hipStream_t st, void* dm = nullptr, uint32_t thr16 = 0,
-                         float drop_scale = 1.f, const int64_t* seed = nullptr, int64_t site = 0);
+                         float drop_scale = 1.f, const int64_t* seed = nullptr, int64_t site = 0,
+                         bool dm_sum = true);   // false: dm without its column partials
 
 // elementwise.hip
 void dltb_gelu_fwd(const void* f, void* g, long n, hipStream_t st);
@@ -202,8 +203,9 @@ struct DltbColRedSeg {
 };
 #endif
 int dltb_colpart_partials(int N);
+// sums = false: GELU / DROP segments only, the elementwise work without column partials (part unused)
 void dltb_colpart(const DltbColPartSeg* segs, int nseg, int P, uint32_t thr16, float drop_scale,
-                  const int64_t* seed, hipStream_t st);
+                  const int64_t* seed, bool sums, hipStream_t st);
 void dltb_colreduce_multi(const DltbColRedSeg* segs, int nseg, hipStream_t st);
 
 // ---- moe.hip: top-k routing with a fixed capacity of C slots per expert (rows = E * C); N token rows of width d
@@ -269,10 +271,12 @@ int dltb_gemm_nn(const void* a, const void* b, void* c, float* part, long lda, l
                  int K, int splits, int cfg, int gm, const float* alpha, hipStream_t st);
 
 // ---- gemm_tn.hip: C[b][M][N] (+)= A[b][K][M]^T B[b][K][N] (weight gradients dY^T X), bf16, 256 x 256 tiles,
-// M, N multiples of 256, K of 64 (>= 128)
+// M, N multiples of 256, K of 64 (>= 128).  colsum (or null): 16-bit [batch][M] at batch stride scs,
+// colsum[b][m] (+)= sum_k A[b][k][m] (the bias gradient of the same linear), fp32 sum rounded once
 bool dltb_gemm_tn_supported(int M, int N, int K);
 int dltb_gemm_tn(const void* a, const void* b, void* c, long lda, long ldb, long ldc, long sa, long sb, long sc,
-                 int M, int N, int K, int batch, int accumulate, hipStream_t st);
+                 int M, int N, int K, int batch, int accumulate, void* colsum, long scs, int cs_accumulate,
+                 hipStream_t st);
 
 // ---- gemm_rs.hip: C[M,N] = A[M][K] B[N][K]^T (+bias) (+C), bf16, register-staged operands (the step's per-layer kernel)
 int dltb_gemm_rs_pick(int M, int N, int K);

@@ -259,7 +259,8 @@ constexpr size_t kFoldLdsMax = 128 * 1024;
 // XS (extra column sum): 0 none; 1 the stored dx; 2 the dropout backward of dx, dm = keep * dx / (1-p)
 // with the keep bits of dropout site `site` (bitwise the colpart DROP kernel's dm), stored to `dm`,
 // and its column sums -- the gradient of the previous block's MLP dropout and fc2 bias, produced
-// here while dx is in registers (one colpart launch less per layer).
+// here while dx is in registers (one colpart launch less per layer); 3 that dm without its column sums
+// (the window-wide dW GEMM forms the fc2 bias gradient, gemm_tn.hip COLSUM): no accumulator, no fold, no partial.
 template <int NV, bool RMS, bool HAS_RES_GRAD, int XS>
 __global__ __launch_bounds__(kFusedWaves * 64) void norm_bwd_fused_kernel(
     const bf16_t* __restrict__ dy, const bf16_t* __restrict__ s, const bf16_t* __restrict__ w,
@@ -269,9 +270,9 @@ __global__ __launch_bounds__(kFusedWaves * 64) void norm_bwd_fused_kernel(
     int64_t site, bool one_fold) {
   // [kFusedWaves][d], or [K][kFusedWaves][d] with one_fold (all partial images folded after one barrier)
   extern __shared__ __attribute__((aligned(16))) float fold[];
-  constexpr bool DXSUM = XS != 0;
+  constexpr bool DXSUM = XS == 1 || XS == 2, DROP = XS >= 2;
   constexpr int K = (RMS ? 1 : 2) + (DXSUM ? 1 : 0);
-  const uint64_t dseed = (XS == 2 && thr16) ? site_seed(seed_ptr, site) : 0ull;
+  const uint64_t dseed = (DROP && thr16) ? site_seed(seed_ptr, site) : 0ull;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nvec = d >> 3;
   float wv[NV][8], acc[K][NV][8];
@@ -335,9 +336,9 @@ __global__ __launch_bounds__(kFusedWaves * 64) void norm_bwd_fused_kernel(
         }
         const uint4 ov = pack8(o);
         *reinterpret_cast<uint4*>(dx + base + idx * 8) = ov;
-        if (DXSUM) {
+        if (DXSUM || DROP) {
           unpack8(ov, o);                                // sum the rounded dx the next GEMM reads
-          if (XS == 2) {
+          if (DROP) {
             if (thr16) {
               const uint32_t rk = rng_row_key(dseed, (uint32_t)row);
 #pragma unroll
@@ -349,10 +350,12 @@ __global__ __launch_bounds__(kFusedWaves * 64) void norm_bwd_fused_kernel(
             }
             const uint4 mv = pack8(o);
             *reinterpret_cast<uint4*>(dm + base + idx * 8) = mv;
-            unpack8(mv, o);                              // sum the rounded dm the fc2 GEMMs read
+            if (DXSUM) unpack8(mv, o);                   // sum the rounded dm the fc2 GEMMs read
           }
+          if (DXSUM) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) acc[K - 1][j][e] += o[e];
+            for (int e = 0; e < 8; ++e) acc[K - 1][j][e] += o[e];
+          }
         }
       }
     }
@@ -670,7 +673,7 @@ void launch_bwd_fused(int N, int d, hipStream_t st, const bf16_t* dy, const bf16
                       const float* mean, const float* rstd, const bf16_t* dres, bf16_t* dx, float* part,
                       const FusedDrop& fd) {
   const int rpw = dltb_norm_bwd_fused_rpw(N);
-  constexpr int K = (RMS ? 1 : 2) + (XS ? 1 : 0);
+  constexpr int K = (RMS ? 1 : 2) + ((XS == 1 || XS == 2) ? 1 : 0);
   const size_t one = (size_t)K * kFusedWaves * d * sizeof(float);
   const bool one_fold = one <= kFoldLdsMax;
   if (one_fold && one > 65536) allow_dynamic_lds<norm_bwd_fused_kernel<NV, RMS, RES, XS>>((int)kFoldLdsMax);
@@ -682,7 +685,8 @@ template <int NV, bool RMS, bool RES>
 void launch_bwd_fused_xs(int xs, int N, int d, hipStream_t st, const bf16_t* dy, const bf16_t* s,
                          const bf16_t* w, const float* mean, const float* rstd, const bf16_t* dres,
                          bf16_t* dx, float* part, const FusedDrop& fd) {
-  if (xs == 2) launch_bwd_fused<NV, RMS, RES, 2>(N, d, st, dy, s, w, mean, rstd, dres, dx, part, fd);
+  if (xs == 3) launch_bwd_fused<NV, RMS, RES, 3>(N, d, st, dy, s, w, mean, rstd, dres, dx, part, fd);
+  else if (xs == 2) launch_bwd_fused<NV, RMS, RES, 2>(N, d, st, dy, s, w, mean, rstd, dres, dx, part, fd);
   else if (xs == 1) launch_bwd_fused<NV, RMS, RES, 1>(N, d, st, dy, s, w, mean, rstd, dres, dx, part, fd);
   else launch_bwd_fused<NV, RMS, RES, 0>(N, d, st, dy, s, w, mean, rstd, dres, dx, part, fd);
 }
@@ -698,7 +702,7 @@ void launch_bwd_fused_nv(bool res, int xs, int N, int d, hipStream_t st, const b
 bool dltb_norm_bwd_fused(const void* dy, const void* s, const void* w, const float* mean,
                          const float* rstd, const void* dres, void* dx, float* part, int N, int d,
                          bool rms, bool dxsum, hipStream_t st, void* dm, uint32_t thr16, float drop_scale,
-                         const int64_t* seed, int64_t site) {
+                         const int64_t* seed, int64_t site, bool dm_sum) {
   if (!dltb_norm_bwd_fused_supported(d)) return false;
   auto DY = (const bf16_t*)dy;
   auto S = (const bf16_t*)s;
@@ -706,7 +710,7 @@ bool dltb_norm_bwd_fused(const void* dy, const void* s, const void* w, const flo
   auto DR = (const bf16_t*)dres;
   auto DX = (bf16_t*)dx;
   const bool res = dres != nullptr;
-  const int xs = dm != nullptr ? 2 : (dxsum ? 1 : 0);
+  const int xs = dm != nullptr ? (dm_sum ? 2 : 3) : (dxsum ? 1 : 0);
   const FusedDrop fd{(bf16_t*)dm, thr16, drop_scale, seed, site};
 #define DLTB_NBF(NVV)                                                                                    \
   do {                                                                                                   \

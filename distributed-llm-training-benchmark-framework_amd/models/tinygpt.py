@@ -182,12 +182,20 @@ class _BlockFn(torch.autograd.Function):
         s = [rt.grad_slot(unit, j) for j in range(12)]
         lb = ctx.lb
 
+        # window-wide dW with the engine's bias_from_dw: the product over the window's dY also writes the
+        # linear's bias gradient (slot j + 1), so no producer below forms bias partials in any micro-step
+        wbias = lb is not None and lb.window and getattr(rt, "bias_from_dw", False)
+
         def wgrad(j, dy, xin, names):      # dW_j (+)= dy^T xin: now, or queued and batched by the engine
             if lb is not None and lb.window:    # window-wide: once, at the last micro-step, all tokens
                 if lb.full is not None:
-                    rt.wgrad(unit, j, getattr(lb.full, names[0]), getattr(lb.full, names[1]), s[j][0], False)
+                    rt.wgrad(unit, j, getattr(lb.full, names[0]), getattr(lb.full, names[1]), s[j][0], False,
+                             bias=(s[j + 1][0], False) if wbias else None)
                 return
             rt.wgrad(unit, j, dy, xin, s[j][0], s[j][1])
+
+        def bslot(j):                      # the bias slot a producer kernel sums into, or None
+            return None if wbias else s[j][0]
 
         # the 8 bias / LayerNorm column sums: fused partials, reduced by ONE launch per block (or,
         # with the engine's shared reducer at world size 1, one launch for all blocks)
@@ -197,21 +205,21 @@ class _BlockFn(torch.autograd.Function):
         if dm_in is not None:
             dm = dm_in
         else:
-            dm = F_.dropout_bwd_bias(dx2, p, rt.seed, model.site_mlp(i), s[11][0], s[11][1], red,
+            dm = F_.dropout_bwd_bias(dx2, p, rt.seed, model.site_mlp(i), bslot(11), s[11][1], red,
                                      out=lb and lb.dm)
         wgrad(10, dm, g, ("dm", "g"))
         w2t = rt.weight_t(unit, 10, w2)
         df = None
         if ctx.dgelu:                   # f holds GELU'(f): dGELU and the fc1 bias partials in the GEMM epilogue
-            df = F_.dgelu_backward(dm, w2, w2t, f, s[9][0], s[9][1], red, out=lb and lb.df)
+            df = F_.dgelu_backward(dm, w2, w2t, f, bslot(9), s[9][1], red, out=lb and lb.df)
         else:
             dg = F_.linear_dgrad(dm, w2, w2t)
-            df = F_.gelu_bwd(dg, f, s[9][0], s[9][1], red, out=lb and lb.df)
+            df = F_.gelu_bwd(dg, f, bslot(9), s[9][1], red, out=lb and lb.df)
         wgrad(8, df, h2, ("df", "h2"))
         w1t = rt.weight_t(unit, 8, w1)
         dh2 = F_.linear_dgrad(df, w1, w1t)
         dx1 = F_.norm_bwd(dh2, x1, ln2w, mean2, rstd2, dx2, s[6][0], s[7][0], s[6][1], False,
-                          red, bias=("dx", s[5][0], s[5][1]), dx_out=lb and lb.dx1)
+                          red, bias=None if wbias else ("dx", s[5][0], s[5][1]), dx_out=lb and lb.dx1)
         # attention
         wgrad(4, dx1, o, ("dx1", "o"))
         do = F_.linear_dgrad(dx1, wo, rt.weight_t(unit, 4, wo))
@@ -229,9 +237,9 @@ class _BlockFn(torch.autograd.Function):
             # profiles/fused_dropout_bwd_ab_r6.txt)
             ps = rt.grad_slot(model.unit_blocks[i - 1], 11)
             plb = model.layer_buffer(i - 1) if lb is not None else None
-            drop_prev = (p, rt.seed, model.site_mlp(i - 1), plb and plb.dm, ps[0], ps[1])
+            drop_prev = (p, rt.seed, model.site_mlp(i - 1), plb and plb.dm, None if wbias else ps[0], ps[1])
         dx = F_.norm_bwd(dh1, x, ln1w, mean1, rstd1, dx1, s[0][0], s[1][0], s[0][1], False,
-                         red, bias=(dqkv, s[3][0], s[3][1]), drop=drop_prev)
+                         red, bias=None if wbias else (dqkv, s[3][0], s[3][1]), drop=drop_prev)
         dm_prev = None
         if drop_prev is not None:
             dx, dm_prev = dx

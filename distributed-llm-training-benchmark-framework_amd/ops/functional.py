@@ -124,18 +124,20 @@ def norm_bwd(dy, s, w, mean, rstd, dres, gw, gb, accumulate, rms, red=None, bias
 
     ``drop=(p, seed, site, dm_out, db, db_acc)``: also return dm = Dropout_backward(dx) of dropout
     site ``site`` with its column sum into ``db`` -- ``(dx, dm)`` -- fused into the same kernel on
-    the GPU (the previous block's MLP dropout and fc2 bias gradient)."""
+    the GPU (the previous block's MLP dropout and fc2 bias gradient).  ``db=None``: dm alone, no column
+    sums (the bias gradient comes from the window-wide dW product, parallel/wgrad.py)."""
     if drop is not None:
         dp, dseed, dsite, dm_out, db, db_acc = drop
         if red is not None and _gpu(dy) and ext().norm_bwd_fused_supported(dy.shape[-1]):
             C = ext()
             dm = torch.empty_like(s) if dm_out is None else dm_out
             dx, part = C.norm_bwd_fused(dy, s, w, mean, rstd, dres, rms, False, dx_out, dm, dp,
-                                        _sd(dseed) if dp > 0 else None, dsite)
+                                        _sd(dseed) if dp > 0 else None, dsite, db is not None)
             red.add(part[0], gw, accumulate)
             if not rms:
                 red.add(part[1], gb, accumulate)
-            red.add(part[-1], db, db_acc)
+            if db is not None:                       # (None: the kernel's no-sum variant, dm alone)
+                red.add(part[-1], db, db_acc)
             if bias is not None and bias[1] is not None:
                 assert not isinstance(bias[0], str), "drop and a dx bias sum are exclusive"
                 if red.defer_plain:
@@ -276,7 +278,9 @@ def dgelu_backward(dm, w2, w2t, gp, db, accumulate, red, out=None):
     dg = linear_dgrad(dm, w2, w2t)
     res = (dg.float() * gp.float()).to(dg.dtype)
     df = _into(out, res)
-    if red is not None and df.is_cuda:
+    if db is None:
+        pass
+    elif red is not None and df.is_cuda:
         parts = ext().colpart([_PLAIN], [df], [None], [None], [None], [None], 0.0, None, [0])
         red.add(parts[0][0], db, accumulate)
     else:
@@ -285,13 +289,17 @@ def dgelu_backward(dm, w2, w2t, gp, db, accumulate, red, out=None):
 
 
 def gelu_bwd(dg, f, db, accumulate, red=None, out=None):
-    """df = dg * gelu'(f); the fc1 bias gradient colsum(df) is fused (reduced at red.flush())."""
+    """df = dg * gelu'(f); the fc1 bias gradient colsum(df) is fused (reduced at red.flush()).
+    ``db=None`` (with a reducer): df alone, from the colpart kernel's no-sum variant."""
     if _gpu(dg):
         if red is None:
             return _into(out, ext().gelu_bwd(dg, f, db, accumulate))
         df = torch.empty_like(dg) if out is None else out
         extra = _take_row_matched(red, dg, 2)        # deferred plain sums ride along (same row count)
         n = len(extra)
+        if db is None and n == 0:
+            ext().colpart([_GELU], [dg], [f], [df], [None], [None], 0.0, None, [0], sums=False)
+            return df
         parts = ext().colpart([_GELU] + [_PLAIN] * n, [dg] + [e[0] for e in extra], [f] + [None] * n,
                               [df] + [None] * n, [None] * (n + 1), [None] * (n + 1), 0.0, None, [0] * (n + 1))
         red.add(parts[0][0], db, accumulate)
@@ -312,11 +320,16 @@ def _take_row_matched(red, t, limit):
 
 
 def dropout_bwd_bias(g, p, seed, site, db, accumulate, red, out=None):
-    """dm = dropout_mask(g) / (1-p) (the Dropout backward) with colsum(dm) -> db fused."""
+    """dm = dropout_mask(g) / (1-p) (the Dropout backward) with colsum(dm) -> db fused.
+    ``db=None``: dm alone, from the colpart kernel's no-sum variant."""
     if _gpu(g):
         dm = torch.empty_like(g) if out is None else out
         extra = _take_row_matched(red, g, 2)
         n = len(extra)
+        if db is None and n == 0:
+            ext().colpart([_DROP], [g], [None], [dm], [None], [None], p, _sd(seed) if p > 0 else None, [site],
+                          sums=False)
+            return dm
         parts = ext().colpart([_DROP] + [_PLAIN] * n, [g] + [e[0] for e in extra], [None] * (n + 1),
                               [dm] + [None] * n, [None] * (n + 1), [None] * (n + 1), p,
                               _sd(seed) if p > 0 else None, [site] + [0] * n)
@@ -907,8 +920,9 @@ def wgrad_operands(dy2d, x2d):
 _OWN_WGRAD = _os.environ.get("DLTB_OWN_WGRAD", "1") == "1"
 
 
-def own_wgrad(dy, x, dw, accumulate):
-    """dw (+)= dy^T x for batched [b, T, *] views on gemm_tn when the shapes and layouts fit; else False."""
+def own_wgrad(dy, x, dw, accumulate, db=None, db_accumulate=False):
+    """dw (+)= dy^T x for batched [b, T, *] views on gemm_tn when the shapes and layouts fit; else False.
+    ``db`` ([b, M] rows, any row stride): also db (+)= colsum(dy), the bias gradient, from the same launch."""
     if not (_OWN_WGRAD and dy.is_cuda and dy.dtype == x.dtype == dw.dtype and dy.dtype == torch.bfloat16
             and dy.dim() == x.dim() == dw.dim() and dy.dim() in (2, 3)):
         return False
@@ -925,7 +939,13 @@ def own_wgrad(dy, x, dw, accumulate):
     # the step: head 115 vs 121-138 us, M7B 200 vs 229 ms per window (profiles/gemm_tn_r6.txt)
     if dy.dim() != 3 or dy.shape[0] < 2 or (M // 256) * (N // 256) * dy.shape[0] < _cu_count(dy.device):
         return False
-    ext().gemm_tn(dy, x, dw, bool(accumulate))
+    if db is not None:
+        if not (db.is_cuda and db.dtype == dy.dtype and db.dim() == 2 and db.shape == (dy.shape[0], M)
+                and db.stride(1) == 1):
+            return False
+        ext().gemm_tn(dy, x, dw, bool(accumulate), db, bool(db_accumulate))
+    else:
+        ext().gemm_tn(dy, x, dw, bool(accumulate))
     return True
 
 

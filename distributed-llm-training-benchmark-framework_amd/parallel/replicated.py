@@ -199,6 +199,11 @@ class ReplicatedEngine(Engine):
         # inside the GEMM instead of being rounded to bf16 after every micro-step.
         self._window_wgrad = (self.defer_wgrad and self.accum > 1 and (self.world == 1 or self.stage != 2)
                               and bool(cfg.extra.get("window_wgrad", os.environ.get("DLTB_WINDOW_WGRAD", "1") == "1")))
+        # ... and the four bias gradients of a block, the column sums of the same dY operands, come out of
+        # those products (gemm_tn's colsum output: fp32 over the window, rounded once) instead of fused
+        # partials, a reducer segment and a bf16 slot accumulation every micro-step
+        self.bias_from_dw = self._window_wgrad and bool(
+            cfg.extra.get("bias_from_dw", os.environ.get("DLTB_BIAS_FROM_DW", "1") == "1"))
         # world 1: nothing reads a gradient slot before the backward ends, so the bias / norm-weight
         # column sums of ALL blocks are reduced by one or two colreduce_multi launches at its end
         # instead of one launch per block, and the QKV-bias partials of block i ride along with
@@ -271,11 +276,11 @@ class ReplicatedEngine(Engine):
             return True
         return self._is_boundary
 
-    def wgrad(self, unit, i, dy, x, dw, accumulate):
+    def wgrad(self, unit, i, dy, x, dw, accumulate, bias=None):
         if self.defer_wgrad:
-            self._wq.add(unit, i, dy, x, dw, accumulate)
+            self._wq.add(unit, i, dy, x, dw, accumulate, bias)
         else:
-            super().wgrad(unit, i, dy, x, dw, accumulate)
+            super().wgrad(unit, i, dy, x, dw, accumulate, bias)
 
     def wgrad_window(self):
         return (self._window_pos, self.accum) if self._window_wgrad else None

@@ -104,12 +104,20 @@ class ParamRuntime:
         its gradients (``grads_ready``)."""
         return None
 
+    # True (with ``wgrad_window()``): the window-wide dW product also forms the linear's bias gradient,
+    # the column sums of its dY operand (``wgrad(..., bias=...)``), so the model's backward kernels skip
+    # their per-micro-step bias partials
+    bias_from_dw = False
+
     def wgrad(self, unit: Unit, i: int, dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor,
-              accumulate: bool):
-        """Write ``dy^T x`` into gradient slot ``dw`` (``accumulate``: add).  The default issues it
-        now; engines with ``defer_wgrad`` run it later, batched with the other blocks' products."""
+              accumulate: bool, bias=None):
+        """Write ``dy^T x`` into gradient slot ``dw`` (``accumulate``: add) and, with ``bias = (slot,
+        accumulate)``, the column sums of ``dy`` into that bias slot.  The default issues it now; engines
+        with ``defer_wgrad`` run it later, batched with the other blocks' products."""
         from ..ops import functional as F_
         F_.linear_wgrad(dy, x, dw, None, accumulate)
+        if bias is not None:
+            F_.colsum_into(dy, bias[0], bias[1])
 
     def embedding_backward(self, tok, pos, dx: torch.Tensor, idx: torch.Tensor, p: float, seed, site: int):
         """The token-embedding backward: scatter-add the (dropout-backward'd) rows of ``dx`` into the

@@ -473,11 +473,11 @@ class ShardedEngine(Engine):
         if cur < g.total:
             g.grad[cur:g.total].zero_()
 
-    def wgrad(self, unit, i, dy, x, dw, accumulate):
+    def wgrad(self, unit, i, dy, x, dw, accumulate, bias=None):
         if self.defer_wgrad:
-            self._wq.add(unit, i, dy, x, dw, accumulate)
+            self._wq.add(unit, i, dy, x, dw, accumulate, bias)
         else:
-            super().wgrad(unit, i, dy, x, dw, accumulate)
+            super().wgrad(unit, i, dy, x, dw, accumulate, bias)
 
     def grad_reducer(self):
         return self._red

@@ -51,17 +51,40 @@ def strided_batch(ts: List[torch.Tensor], out: bool = False) -> Optional[torch.T
     return t0.as_strided((len(ts),) + tuple(t0.shape), (step,) + tuple(t0.stride()))
 
 
+def strided_rows(ts: List[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A [n, k] view whose rows are the equally spaced, non-overlapping contiguous 1-D tensors ``ts``
+    (in order) of one storage -- the bias slots of one parameter in consecutive blocks -- or None."""
+    t0 = ts[0]
+    if t0.dim() != 1 or t0.stride(0) != 1:
+        return None
+    if len(ts) == 1:
+        return t0.unsqueeze(0)
+    es = t0.element_size()
+    step = ts[1].data_ptr() - t0.data_ptr()
+    if step < t0.numel() * es or step % es:
+        return None
+    base = t0.untyped_storage().data_ptr()
+    for a, b in zip(ts, ts[1:]):
+        if (b.data_ptr() - a.data_ptr() != step or b.shape != t0.shape or b.stride() != t0.stride()
+                or b.untyped_storage().data_ptr() != base):
+            return None
+    return t0.as_strided((len(ts), t0.numel()), (step // es, 1))
+
+
 class WgradQueue:
-    """Queued ``dw (+)= dy^T x`` products keyed by unit; ``flush`` issues them batched."""
+    """Queued ``dw (+)= dy^T x`` products keyed by unit; ``flush`` issues them batched.  A product may
+    carry the linear's bias slot: ``bias = (slot, accumulate)`` gets the column sums of ``dy`` -- from the
+    own kernel's colsum output when the batch runs there, else from one column-sum launch per block."""
 
     def __init__(self):
-        self._items: Dict[int, list] = defaultdict(list)     # id(unit) -> [(i, dy, x, dw, acc)]
+        self._items: Dict[int, list] = defaultdict(list)     # id(unit) -> [(i, dy, x, dw, acc, bias)]
         self.batched_calls = 0
         self.single_calls = 0
         self.tn_calls = 0            # batched products that ran on the own token-major kernel (gemm_tn)
+        self.tn_bias_calls = 0       # ... of them, with the bias gradients from the kernel's colsum output
 
-    def add(self, unit, i, dy, x, dw, accumulate):
-        self._items[id(unit)].append((i, dy, x, dw, bool(accumulate)))
+    def add(self, unit, i, dy, x, dw, accumulate, bias=None):
+        self._items[id(unit)].append((i, dy, x, dw, bool(accumulate), bias))
 
     def has(self, units) -> bool:
         """Whether any of ``units`` has queued products."""
@@ -76,15 +99,17 @@ class WgradQueue:
 
     def flush(self, units=None):
         keys = list(self._items) if units is None else [id(u) for u in units if id(u) in self._items]
-        groups = defaultdict(list)                           # (param index, accumulate) -> items
+        groups = defaultdict(list)                           # (param index, accumulate, bias accumulate) -> items
         for k in keys:
-            for i, dy, x, dw, acc in self._items.pop(k):
-                groups[(i, acc)].append((dy, x, dw))
-        for (_, acc), items in groups.items():
+            for i, dy, x, dw, acc, bias in self._items.pop(k):
+                db, bacc = (None, None) if bias is None else (bias[0], bool(bias[1]))
+                groups[(i, acc, bacc)].append((dy, x, dw, db))
+        for (_, acc, bacc), items in groups.items():
             items.sort(key=lambda it: it[2].data_ptr())      # flat-buffer order of the slots
-            self._issue(items, acc)
+            self._issue(items, acc, bacc)
 
-    def _issue(self, items, acc):
+    def _issue(self, items, acc, bacc=None):
+        """``bacc`` None: no bias slots; else every item carries one, accumulated or overwritten alike."""
         if len(items) > 1:
             DW = strided_batch([it[2] for it in items], out=True)
             DY = strided_batch([it[0] for it in items])
@@ -94,6 +119,12 @@ class WgradQueue:
                     # BLAS TN batched: hipBLASLt's heuristic solution for it faulted the GPU
                     # (profiles/dw_layout_probe_fault_r4.txt); the layer buffers are row-major
                     raise RuntimeError("batched dW with a column-major X operand (BLAS TN) is refused")
+                DB = strided_rows([it[3] for it in items]) if bacc is not None else None
+                if DB is not None and F_.own_wgrad(DY, X, DW, acc, DB, bacc):
+                    self.tn_calls += 1
+                    self.tn_bias_calls += 1
+                    self.batched_calls += 1
+                    return
                 if F_.own_wgrad(DY, X, DW, acc):
                     self.tn_calls += 1
                 elif _blt.mm(DY.transpose(1, 2), X, DW, acc):
@@ -103,7 +134,16 @@ class WgradQueue:
                 else:
                     torch.bmm(DY.transpose(1, 2), X, out=DW)
                 self.batched_calls += 1
+                self._bias(items, bacc)
                 return
-        for dy, x, dw in items:                              # not equally spaced: one GEMM each
+        for dy, x, dw, _ in items:                           # not equally spaced: one GEMM each
             F_.linear_wgrad(dy, x, dw, None, acc)
             self.single_calls += 1
+        self._bias(items, bacc)
+
+    @staticmethod
+    def _bias(items, bacc):
+        """The bias slots of products that did not run on the own kernel's colsum output."""
+        if bacc is not None:
+            for dy, _, _, db in items:
+                F_.colsum_into(dy, db, bacc)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The own weight-gradient GEMM (csrc/gemm_tn.hip) against hipBLASLt on the dW products of a training step.
 
-    python scripts/bench_gemm_tn.py [--iters 10] [--only dw.fc1,head.wgrad]
+    python scripts/bench_gemm_tn.py [--iters 10] [--only dw.fc1,head.wgrad] [--colsum]
 
 Problems (TinyGPT-A, ZeRO-2 at world 1, grad-accum 4): the window-wide batched dW of each parameter kind over
 the 16 blocks (K = 4 x 2048 tokens; operands are views of layer-strided activation buffers, outputs views of
@@ -9,6 +9,8 @@ the flat gradient buffer at the block stride, as parallel/wgrad.py issues them) 
 gradient (V = 32000 x d = 1024 over 2048 tokens); plus two Mistral-7B-shape products.  hipBLASLt runs the
 shipped tuned solution through the extension API when the problem is in configs/blaslt (what the step runs),
 else torch (TunableOp).  Timing: graph replay, interleaved rounds in one process; uniform random operands.
+--colsum: the batched products also with the kernel's column-sum output (the bias gradients) into the slot
+behind each dW slot, as a third interleaved arm.
 """
 import argparse
 import os
@@ -38,11 +40,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--only", default="")
+    ap.add_argument("--colsum", action="store_true")
     a = ap.parse_args()
     C = ext()
     blaslt.load()
     torch.manual_seed(0)
-    tot = [0.0, 0.0]
+    tot = [0.0, 0.0, 0.0]
     for name, B, M, N, K in problems():
         if a.only and name not in a.only.split(","):
             continue
@@ -69,7 +72,16 @@ def main():
 
         def own():
             C.gemm_tn(dy, x, dw_own, False)
-        t_lib, t_own = graph_time([lib, own], a.iters)
+        t_cs = None
+        if a.colsum and B > 1:
+            db = flat2.as_strided((B, M), (BLOCK, 1), M * N)
+
+            def own_cs():
+                C.gemm_tn(dy, x, dw_own, False, db, False)
+            t_lib, t_own, t_cs = graph_time([lib, own, own_cs], a.iters)
+            e_cs = (db.float() - dy.float().sum(1)).abs().max().item()
+        else:
+            t_lib, t_own = graph_time([lib, own], a.iters)
         lib()
         own()
         torch.cuda.synchronize()
@@ -79,14 +91,17 @@ def main():
         fl = 2.0 * B * M * N * K
         print(f"{name:11s} b{B:2d} M{M:6d} N{N:6d} K{K:6d}  hipBLASLt {t_lib:8.1f} us {fl / t_lib / 1e6:6.0f} TF/s "
               f"(err {e_lib:.3g})   own {t_own:8.1f} us {fl / t_own / 1e6:6.0f} TF/s (err {e_own:.3g})  "
-              f"x{t_lib / t_own:4.2f}" + ("  MISMATCH" if e_own > 2 * e_lib + 0.05 else ""),
+              f"x{t_lib / t_own:4.2f}" + ("  MISMATCH" if e_own > 2 * e_lib + 0.05 else "")
+              + (f"   own + colsum {t_cs:8.1f} us ({100 * (t_cs / t_own - 1):+.1f} %, err {e_cs:.3g})" if t_cs else ""),
               flush=True)
         if name.startswith("dw."):
             tot[0] += t_lib
             tot[1] += t_own
+            tot[2] += t_cs or 0.0
         del dy, x
     if tot[0]:
-        print(f"window dW sum: hipBLASLt {tot[0]:.1f} us, own {tot[1]:.1f} us  x{tot[0] / tot[1]:.2f}")
+        print(f"window dW sum: hipBLASLt {tot[0]:.1f} us, own {tot[1]:.1f} us  x{tot[0] / tot[1]:.2f}"
+              + (f", own + colsum {tot[2]:.1f} us ({100 * (tot[2] / tot[1] - 1):+.1f} %)" if tot[2] else ""))
 
 
 if __name__ == "__main__":
