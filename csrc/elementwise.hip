@@ -7,6 +7,7 @@
 //   dropout_add         out = x + dropout(r)                              (residual + Dropout)
 //   dropout_bwd         out = dropout_mask(g) * 1/(1-p)                   (mask regenerated)
 //   swiglu_fwd/bwd      h = silu(gate) * up                               (Mistral-shape FFN)
+//                       <true>: h = gelu_tanh(gate) * up                  (GeGLU, the Gemma FFN)
 //   swiglu_bwd_h        swiglu_bwd that also rebuilds h                   (activation recomputation)
 //   rope_fwd/bwd        rotate-half RoPE in place on the q/k columns of a fused qkv buffer
 //   f32_from_bf16       dst (+)= float(src)
@@ -164,7 +165,29 @@ __global__ __launch_bounds__(256) void dropout_kernel(const bf16_t* __restrict__
 // ------------------------------------------------------------------------------- SwiGLU
 DLTB_DEV float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
 
-// gu: [N, 2F] = [gate | up]; h: [N, F]
+// GeGLU (the GEGLU = true instantiations below): gelu_tanh(g) = 0.5 g (1 + t), t = tanh(k (g + c g^3)),
+// k = sqrt(2 / pi), c = 0.044715.  The tanh in the form of csrc/attention.hip's CAP kernels,
+// t = 1 - 2 rcp(1 + exp2(2 log2(e) u)): exactly +-1 when the exp2 saturates (u = +-inf included, which
+// g^2 overflowing fp32 gives).  Returns hp = 0.5 (1 + t), so gelu_tanh(g) = g * hp, and in *grad
+//     d gelu_tanh / dg = hp + 0.5 g (1 - t^2) k (1 + 3 c g^2),
+// whose second term is taken as exactly 0 where 1 - t^2 = 0 (t = +-1: 0 * inf otherwise, once g^2 overflows).
+// With |t| < 1 in fp32, |u| < 9 and |g| < 6: nothing overflows in that branch.
+DLTB_DEV float gelu_tanh_half(float g, float* grad) {
+  const float kK = 0.7978845608028654f, kC = 0.044715f;
+  const float g2 = g * g;
+  const float u = kK * (g * __builtin_fmaf(kC, g2, 1.f));
+  const float r = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(2.8853900817779268f * u));
+  const float t = __builtin_fmaf(-2.f, r, 1.f);
+  const float hp = 0.5f * (1.f + t);
+  if (grad) {
+    const float q = __builtin_fmaf(-t, t, 1.f);
+    *grad = q == 0.f ? hp : __builtin_fmaf(0.5f * g * q, kK * __builtin_fmaf(3.f * kC, g2, 1.f), hp);
+  }
+  return hp;
+}
+
+// gu: [N, 2F] = [gate | up]; h: [N, F].  GEGLU: the activation, a compile-time switch of the three kernels
+template <bool GEGLU>
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const bf16_t* __restrict__ gu,
                                                         bf16_t* __restrict__ h, int N, int F) {
   const long n8 = (long)N * F / 8;
@@ -175,12 +198,18 @@ __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const bf16_t* __restric
     float g[8], u[8], o[8];
     unpack8(ld16<uint4>(gu + row * 2 * F + c), g);
     unpack8(ld16<uint4>(gu + row * 2 * F + F + c), u);
+    if (GEGLU) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = g[e] * sigmoid_f(g[e]) * u[e];
+      for (int e = 0; e < 8; ++e) o[e] = g[e] * gelu_tanh_half(g[e], nullptr) * u[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = g[e] * sigmoid_f(g[e]) * u[e];
+    }
     *reinterpret_cast<uint4*>(h + row * F + c) = pack8(o);
   }
 }
 
+template <bool GEGLU>
 __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* __restrict__ dh,
                                                         const bf16_t* __restrict__ gu,
                                                         bf16_t* __restrict__ dgu, int N, int F) {
@@ -193,12 +222,22 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* __restric
     unpack8(ld16<uint4>(gu + row * 2 * F + c), g);
     unpack8(ld16<uint4>(gu + row * 2 * F + F + c), u);
     unpack8(ld16<uint4>(dh + row * F + c), d);
+    if (GEGLU) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float s = sigmoid_f(g[e]);
-      const float silu = g[e] * s;
-      du[e] = d[e] * silu;
-      dg[e] = d[e] * u[e] * s * (1.f + g[e] * (1.f - s));
+      for (int e = 0; e < 8; ++e) {
+        float gr;                                        // (dh * gelu') * up: dh * up alone may overflow where gelu' = 0
+        const float act = g[e] * gelu_tanh_half(g[e], &gr);
+        du[e] = d[e] * act;
+        dg[e] = d[e] * gr * u[e];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float s = sigmoid_f(g[e]);
+        const float silu = g[e] * s;
+        du[e] = d[e] * silu;
+        dg[e] = d[e] * u[e] * s * (1.f + g[e] * (1.f - s));
+      }
     }
     *reinterpret_cast<uint4*>(dgu + row * 2 * F + c) = pack8(dg);
     *reinterpret_cast<uint4*>(dgu + row * 2 * F + F + c) = pack8(du);
@@ -208,6 +247,7 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* __restric
 // swiglu_bwd that also rebuilds h = silu(gate) * up (activation recomputation: the forward did not keep h):
 // gate | up and dh are read once for both outputs, instead of a swiglu_fwd launch re-reading gu.  The
 // expressions are the two kernels' above, so h is bitwise swiglu_fwd's and dgu bitwise swiglu_bwd's.
+template <bool GEGLU>
 __global__ __launch_bounds__(256) void swiglu_bwd_h_kernel(const bf16_t* __restrict__ dh,
                                                           const bf16_t* __restrict__ gu,
                                                           bf16_t* __restrict__ dgu, bf16_t* __restrict__ h,
@@ -221,13 +261,24 @@ __global__ __launch_bounds__(256) void swiglu_bwd_h_kernel(const bf16_t* __restr
     unpack8(ld16<uint4>(gu + row * 2 * F + c), g);
     unpack8(ld16<uint4>(gu + row * 2 * F + F + c), u);
     unpack8(ld16<uint4>(dh + row * F + c), d);
+    if (GEGLU) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float s = sigmoid_f(g[e]);
-      const float silu = g[e] * s;
-      o[e] = silu * u[e];
-      du[e] = d[e] * silu;
-      dg[e] = d[e] * u[e] * s * (1.f + g[e] * (1.f - s));
+      for (int e = 0; e < 8; ++e) {
+        float gr;
+        const float act = g[e] * gelu_tanh_half(g[e], &gr);
+        o[e] = act * u[e];
+        du[e] = d[e] * act;
+        dg[e] = d[e] * gr * u[e];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float s = sigmoid_f(g[e]);
+        const float silu = g[e] * s;
+        o[e] = silu * u[e];
+        du[e] = d[e] * silu;
+        dg[e] = d[e] * u[e] * s * (1.f + g[e] * (1.f - s));
+      }
     }
     *reinterpret_cast<uint4*>(h + row * F + c) = pack8(o);
     *reinterpret_cast<uint4*>(dgu + row * 2 * F + c) = pack8(dg);
@@ -417,19 +468,33 @@ void dltb_dropout(const void* x, const void* r, void* out, long n, int cols, uin
                        (const bf16_t*)r, (bf16_t*)out, n8, cols, thr16, scale, seed, site);
 }
 
-void dltb_swiglu_fwd(const void* gu, void* h, int N, int F, hipStream_t st) {
-  hipLaunchKernelGGL(swiglu_fwd_kernel, dim3(ew_grid((long)N * F / 8)), dim3(256), 0, st,
-                     (const bf16_t*)gu, (bf16_t*)h, N, F);
+void dltb_swiglu_fwd(const void* gu, void* h, int N, int F, hipStream_t st, bool geglu) {
+  const dim3 grid(ew_grid((long)N * F / 8));
+  if (geglu)
+    hipLaunchKernelGGL(swiglu_fwd_kernel<true>, grid, dim3(256), 0, st, (const bf16_t*)gu, (bf16_t*)h, N, F);
+  else
+    hipLaunchKernelGGL(swiglu_fwd_kernel<false>, grid, dim3(256), 0, st, (const bf16_t*)gu, (bf16_t*)h, N, F);
 }
 
-void dltb_swiglu_bwd(const void* dh, const void* gu, void* dgu, int N, int F, hipStream_t st) {
-  hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(ew_grid((long)N * F / 8)), dim3(256), 0, st,
-                     (const bf16_t*)dh, (const bf16_t*)gu, (bf16_t*)dgu, N, F);
+void dltb_swiglu_bwd(const void* dh, const void* gu, void* dgu, int N, int F, hipStream_t st, bool geglu) {
+  const dim3 grid(ew_grid((long)N * F / 8));
+  if (geglu)
+    hipLaunchKernelGGL(swiglu_bwd_kernel<true>, grid, dim3(256), 0, st, (const bf16_t*)dh, (const bf16_t*)gu,
+                       (bf16_t*)dgu, N, F);
+  else
+    hipLaunchKernelGGL(swiglu_bwd_kernel<false>, grid, dim3(256), 0, st, (const bf16_t*)dh, (const bf16_t*)gu,
+                       (bf16_t*)dgu, N, F);
 }
 
-void dltb_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, int N, int F, hipStream_t st) {
-  hipLaunchKernelGGL(swiglu_bwd_h_kernel, dim3(ew_grid((long)N * F / 8)), dim3(256), 0, st,
-                     (const bf16_t*)dh, (const bf16_t*)gu, (bf16_t*)dgu, (bf16_t*)h, N, F);
+void dltb_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, int N, int F, hipStream_t st,
+                       bool geglu) {
+  const dim3 grid(ew_grid((long)N * F / 8));
+  if (geglu)
+    hipLaunchKernelGGL(swiglu_bwd_h_kernel<true>, grid, dim3(256), 0, st, (const bf16_t*)dh, (const bf16_t*)gu,
+                       (bf16_t*)dgu, (bf16_t*)h, N, F);
+  else
+    hipLaunchKernelGGL(swiglu_bwd_h_kernel<false>, grid, dim3(256), 0, st, (const bf16_t*)dh, (const bf16_t*)gu,
+                       (bf16_t*)dgu, (bf16_t*)h, N, F);
 }
 
 void dltb_rope(void* qkv, const float* cosb, const float* sinb, int N, int T, int heads, int D,

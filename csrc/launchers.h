@@ -48,10 +48,12 @@ void dltb_colsum(const void* src, float* part, void* out, int accumulate, int N,
                  hipStream_t st);
 void dltb_dropout(const void* x, const void* r, void* out, long n, int cols, uint32_t thr16,
                   float scale, const int64_t* seed, int64_t site, hipStream_t st);
-void dltb_swiglu_fwd(const void* gu, void* h, int N, int F, hipStream_t st);
-void dltb_swiglu_bwd(const void* dh, const void* gu, void* dgu, int N, int F, hipStream_t st);
+// geglu: the gate's activation is gelu_tanh instead of SiLU (the GEGLU instantiations)
+void dltb_swiglu_fwd(const void* gu, void* h, int N, int F, hipStream_t st, bool geglu = false);
+void dltb_swiglu_bwd(const void* dh, const void* gu, void* dgu, int N, int F, hipStream_t st, bool geglu = false);
 // swiglu_bwd plus h = swiglu_fwd(gu) rebuilt in the same pass (activation recomputation)
-void dltb_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, int N, int F, hipStream_t st);
+void dltb_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, int N, int F, hipStream_t st,
+                       bool geglu = false);
 void dltb_rope(void* qkv, const float* cosb, const float* sinb, int N, int T, int heads, int D,
                int stride, bool inverse, hipStream_t st);
 void dltb_f32_from_bf16(float* dst, const void* src, long n, int accumulate, hipStream_t st);
@@ -69,6 +71,18 @@ int dltb_qknorm_partials(int N);    // G: workgroups of the backward = rows of p
 void dltb_qknorm_rope_bwd(void* dqkv, const void* raw, const void* wq, const void* wk, const float* cosb,
                           const float* sinb, float* part_q, float* part_k, int N, int T, int Hq, int Hkv, int D,
                           int stride, float eps, hipStream_t st);
+
+// sandwich_norm.hip: "normalise, then add".  s = x + RMSNorm(a; w_out); with w_next also y = RMSNorm(s; w_next) of
+// the stored s and rstd_s (w_next == nullptr: y and rstd_s are not touched).  d % 8 == 0, d <= 4096
+void dltb_sandwich_fwd(const void* x, const void* a, const void* w_out, const void* w_next, void* s, void* y,
+                       float* rstd_a, float* rstd_s, int N, int d, float eps, hipStream_t st);
+// the backward of the w_next form: dx = dres + RMSNormBwd(dy; s), da = RMSNormBwd(dx; a) of the stored dx, and the
+// fp32 partials part[2][blocks(N)][d] of the w_next and the w_out gradient.  d % 8 == 0, d <= 2048 (else false)
+bool dltb_sandwich_bwd_supported(int d);
+int dltb_sandwich_bwd_blocks(int N);
+bool dltb_sandwich_bwd(const void* dy, const void* s, const void* w_next, const float* rstd_s, const void* dres,
+                       const void* a, const void* w_out, const float* rstd_a, void* dx, void* da, float* part,
+                       int N, int d, hipStream_t st);
 
 // comm_emu.hip: one emulated RCCL collective (DLTB_COMM=emulate:N) -- `channels` paced workgroups
 // that read `traffic` (`passes` times) and write dst[r * rep_stride + j] = scale * src[j]

@@ -16,7 +16,7 @@ Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
 --doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk, --moe-experts, --moe-top-k,
 --moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef, --moe-dropless, --qk-norm,
---attn-sinks, --attn-softcap, --final-softcap, --lm-z-loss-coef.
+--attn-sinks, --attn-softcap, --final-softcap, --lm-z-loss-coef, --sandwich-norm, --ffn-act.
 """
 import argparse
 import json
@@ -112,6 +112,14 @@ def build_parser():
                    help="causal tiers: one learned sink logit per query head and layer that joins the attention "
                         "softmax's denominator and carries no value (gpt-oss style), taken in by the forward "
                         "attention kernel's epilogue; default: off")
+    p.add_argument("--sandwich-norm", action="store_true",
+                   help="causal tiers: every sublayer's output goes through its own RMSNorm before it joins the "
+                        "residual stream (Gemma-2 / Gemma-3 sandwich norms; the placement of OLMo-2 and Grok-1), two "
+                        "more [n_embd] weights per layer, fused with the residual add and the next pre-norm; "
+                        "default: off")
+    p.add_argument("--ffn-act", choices=["swiglu", "geglu"], default="swiglu",
+                   help="causal tiers: the gated FFN's activation, silu(gate) * up or gelu_tanh(gate) * up (the Gemma "
+                        "FFN), dense and mixture-of-experts; default: swiglu")
     p.add_argument("--attn-softcap", type=float, default=0.0, metavar="C",
                    help="causal tiers: attention logit soft-capping, every score x becomes C * tanh(x / C) before the "
                         "softmax (Gemma-2 uses 50), in capped instantiations of the three attention kernels; not "
@@ -257,6 +265,29 @@ def check_qk_norm(on, mcfg, tier):
         raise ValueError(f"--qk-norm needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the reference's "
                          "attention with learned positions and no RoPE")
     mcfg.qk_norm = True
+    mcfg.validate()
+
+
+def check_sandwich_norm(on, mcfg, tier):
+    """ValueError when ``--sandwich-norm`` is set for a tier without the causal decoder block; sets it on ``mcfg``."""
+    if not on:
+        return
+    if not mcfg.causal:
+        raise ValueError(f"--sandwich-norm needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the "
+                         "reference's LayerNorm block")
+    mcfg.sandwich_norm = True
+    mcfg.validate()
+
+
+def check_ffn_act(act, mcfg, tier):
+    """ValueError when ``--ffn-act`` is not swiglu for a tier without the gated FFN; sets it on ``mcfg``."""
+    act = act or "swiglu"
+    if act == "swiglu":
+        return
+    if not mcfg.causal:
+        raise ValueError(f"--ffn-act {act} needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the "
+                         "reference's GELU MLP without a gate")
+    mcfg.ffn_act = act
     mcfg.validate()
 
 
@@ -430,6 +461,8 @@ def train(args):
                   bool(getattr(args, "moe_dropless", False)))
         check_qk_norm(bool(getattr(args, "qk_norm", False)), mcfg, args.tier)
         check_attn_sinks(bool(getattr(args, "attn_sinks", False)), mcfg, args.tier)
+        check_sandwich_norm(bool(getattr(args, "sandwich_norm", False)), mcfg, args.tier)
+        check_ffn_act(getattr(args, "ffn_act", "swiglu"), mcfg, args.tier)
         check_attn_softcap(getattr(args, "attn_softcap", 0.0), bool(getattr(args, "attn_sinks", False)), mcfg,
                            args.tier)
         check_final_softcap(getattr(args, "final_softcap", 0.0), mcfg, args.tier)
@@ -465,6 +498,9 @@ def train(args):
                   f"{mcfg.moe_z_loss_coef}", flush=True)
         if mcfg.qk_norm and is_main:
             print(f"QK-norm: RMSNorm over head_dim {mcfg.head_dim} on q and k, fused with RoPE", flush=True)
+        if (mcfg.sandwich_norm or mcfg.ffn_act != "swiglu") and is_main:
+            print(f"decoder block: sandwich norms {'on' if mcfg.sandwich_norm else 'off'} (an RMSNorm on every "
+                  f"sublayer's output before the residual add), gated FFN activation {mcfg.ffn_act}", flush=True)
         if mcfg.attn_sinks and is_main:
             print(f"attention sinks: one learned logit per query head ({mcfg.n_head} per layer)", flush=True)
         if mcfg.attn_softcap and is_main:
@@ -636,6 +672,7 @@ def train(args):
             "activation_recompute": recompute,
             "head_chunk": head_chunk, "head_chunks": n_head_chunks,
             "attn_sinks": bool(mcfg.attn_sinks),
+            "sandwich_norm": bool(mcfg.sandwich_norm), "ffn_act": str(mcfg.ffn_act),
             "attn_softcap": float(mcfg.attn_softcap),
             "final_softcap": float(mcfg.final_softcap),
             "lm_z_loss_coef": float(mcfg.lm_z_loss_coef),
@@ -739,6 +776,8 @@ def main(argv=None):
     try:
         check_qk_norm(args.qk_norm, get_model_config(args.tier, args.seq_len), args.tier)
         check_attn_sinks(args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
+        check_sandwich_norm(args.sandwich_norm, get_model_config(args.tier, args.seq_len), args.tier)
+        check_ffn_act(args.ffn_act, get_model_config(args.tier, args.seq_len), args.tier)
         check_attn_softcap(args.attn_softcap, args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
         check_final_softcap(args.final_softcap, get_model_config(args.tier, args.seq_len), args.tier)
         check_lm_z_loss(args.lm_z_loss_coef, get_model_config(args.tier, args.seq_len), args.tier)

@@ -18,6 +18,9 @@ from dataclasses import dataclass, field, asdict
 from typing import Optional
 
 
+FFN_ACTS = ("swiglu", "geglu")
+
+
 @dataclass
 class ModelConfig:
     arch: str = "tinygpt"            # "tinygpt" | "mistral"
@@ -72,6 +75,14 @@ class ModelConfig:
     # z-loss on the LM head (mistral arch; PaLM, OLMo-2, Chameleon use about 1e-4): the loss gains
     # lm_z_loss_coef * mean over the valid rows of logsumexp(logits)^2 (of the capped logits under final_softcap); 0 = off
     lm_z_loss_coef: float = 0.0
+    # sandwich norms (mistral arch; Gemma-2 / Gemma-3, the placement of OLMo-2 and Grok-1): every sublayer's output goes
+    # through its own RMSNorm before it joins the residual stream, x1 = x + RMSNorm(attn), x2 = x1 + RMSNorm(ffn), on top
+    # of the two pre-norms; two [n_embd] weights per layer, self_attn.out_norm.weight and mlp.out_norm.weight,
+    # initialised to ones (csrc/sandwich_norm.hip)
+    sandwich_norm: bool = False
+    # the gated FFN's activation (mistral arch): "swiglu" = silu(gate) * up, "geglu" = gelu_tanh(gate) * up (Gemma);
+    # the GEGLU instantiations of the three gated-FFN kernels (csrc/elementwise.hip), dense and both MoE routings
+    ffn_act: str = "swiglu"
 
     def __post_init__(self):
         self.validate()
@@ -115,6 +126,16 @@ class ModelConfig:
                 raise ValueError(f"{name} must be a finite number >= 0 (0 = off), got {c!r}")
             if c > 0 and self.arch != "mistral":
                 raise ValueError(f"{name} ({what}) needs the mistral arch, got arch {self.arch!r}")
+        if not isinstance(self.sandwich_norm, bool):
+            raise ValueError(f"sandwich_norm must be a bool, got {self.sandwich_norm!r}")
+        if self.sandwich_norm and self.arch != "mistral":
+            raise ValueError(f"sandwich_norm (an RMSNorm on every sublayer's output) needs the mistral arch, got arch "
+                             f"{self.arch!r}")
+        if self.ffn_act not in FFN_ACTS:
+            raise ValueError(f"ffn_act must be one of {', '.join(FFN_ACTS)}, got {self.ffn_act!r}")
+        if self.ffn_act != "swiglu" and self.arch != "mistral":
+            raise ValueError(f"ffn_act = {self.ffn_act!r} (the gated FFN's activation) needs the mistral arch, got arch "
+                             f"{self.arch!r}")
         k, cf = self.moe_top_k, self.moe_capacity_factor
         if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4):
             raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
@@ -184,6 +205,8 @@ class ModelConfig:
         per_block = d + (d * d + 2 * kvd * d) + d * d + d + ffn
         if self.qk_norm:         # the q and the k weight, [head_dim] each
             per_block += 2 * hd
+        if self.sandwich_norm:   # the attention site's and the FFN site's output norm, [n_embd] each
+            per_block += 2 * d
         if self.attn_sinks:      # one sink logit per query head
             per_block += self.n_head
         head = 0 if self.tie_embeddings else V * d
@@ -198,7 +221,8 @@ class ModelConfig:
         FFN term counts ``moe_top_k`` experts and the router product per token.  ``qk_norm`` changes nothing here: it
         adds no matrix product (its 2 * head_dim weights per layer are elementwise), like the other norms; nor does
         ``attn_sinks`` (one more softmax term per query row and head), ``attn_softcap`` (elementwise on the
-        scores) or ``final_softcap`` / ``lm_z_loss_coef`` (elementwise on the logits, inside the loss kernels)."""
+        scores), ``final_softcap`` / ``lm_z_loss_coef`` (elementwise on the logits, inside the loss kernels),
+        ``sandwich_norm`` (two more row norms per layer) or ``ffn_act`` (elementwise)."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d

@@ -45,6 +45,16 @@ With ``cfg.final_softcap`` = C > 0 the head's loss is formed from ``c = C * tanh
 ``xent_bwd_lse_(..., softcap=, z_coef=)``: the option kernels of csrc/xent.hip), unchunked and under ``head_chunk``.
 c exists in fp32 registers only; the row mean, the 1 / count scale and what the backward keeps are unchanged (the
 kept lse is that of c).  The logits handed back to a caller are the capped ones, rounded to the model's format.
+
+With ``cfg.sandwich_norm`` every sublayer's output goes through its own RMSNorm before it joins the residual stream,
+``x1 = x + RMSNorm(a; self_attn.out_norm)`` and ``x2 = x1 + RMSNorm(m; mlp.out_norm)`` (m: the dense FFN's output or the
+MoE combine), on top of the two pre-norms.  The two [n_embd] weights sit in the layer's parameter list after the
+QK-norm pair and before the sinks.  The attention site is one launch with the next pre-norm (``sandwich_fwd`` /
+``sandwich_bwd``, csrc/sandwich_norm.hip); the FFN site's forward is the same kernel without the second norm and its
+backward a plain ``norm_bwd``.  The layer keeps a, m and their two rstd rows in addition.
+
+With ``cfg.ffn_act = "geglu"`` the gated FFN is ``gelu_tanh(gate) * up`` (``swiglu_fwd`` / ``_bwd`` / ``_bwd_h(...,
+act=)``: the GEGLU instantiations of csrc/elementwise.hip) on the dense path, the recompute path and both MoE routings.
 """
 import math
 
@@ -100,16 +110,23 @@ class MistralLayer(nn.Module):
                                cfg.n_head if cfg.attn_sinks else None)
         self.qk_norm = cfg.qk_norm
         self.attn_sinks = cfg.attn_sinks
+        self.sandwich_norm = cfg.sandwich_norm
         self.post_attention_layernorm = _RMSNorm(d)
         self.mlp = _MoE(d, cfg.ffn_dim, cfg.n_experts) if cfg.n_experts else _MLP(d, cfg.ffn_dim)
+        if cfg.sandwich_norm:   # sandwich norms: one RMSNorm on the attention sublayer's output, one on the FFN's
+            self.self_attn.out_norm = _RMSNorm(d)
+            self.mlp.out_norm = _RMSNorm(d)
 
     def param_list(self):
-        # the QK-norm weights and then the sinks come last, so the dense (4, 5) and MoE (4, 5 + 2e, 6 + 2e) indices
-        # hold with them
+        # the QK-norm weights, then the sandwich norms' pair and then the sinks come last, so the dense (4, 5) and MoE
+        # (4, 5 + 2e, 6 + 2e) indices hold with them
         tail = []
         if self.qk_norm:
             tail = [("self_attn.q_norm.weight", self.self_attn.q_norm.weight),
                     ("self_attn.k_norm.weight", self.self_attn.k_norm.weight)]
+        if self.sandwich_norm:
+            tail = tail + [("self_attn.out_norm.weight", self.self_attn.out_norm.weight),
+                           ("mlp.out_norm.weight", self.mlp.out_norm.weight)]
         if self.attn_sinks:
             tail = tail + [("self_attn.sinks", self.self_attn.sinks)]
         head = [("input_layernorm.weight", self.input_layernorm.weight),
@@ -148,9 +165,9 @@ class _EmbedFn(torch.autograd.Function):
 
 
 def _n_block_weights(cfg, ws):
-    """How many of a layer's parameters ``ws`` come before its tail -- the QK-norm pair, then the sinks -- that is
-    the norms, projections and the FFN."""
-    return len(ws) - (2 if cfg.qk_norm else 0) - (1 if cfg.attn_sinks else 0)
+    """How many of a layer's parameters ``ws`` come before its tail -- the QK-norm pair, then the sandwich norms'
+    pair, then the sinks -- that is the norms, projections and the FFN."""
+    return len(ws) - (2 if cfg.qk_norm else 0) - (2 if cfg.sandwich_norm else 0) - (1 if cfg.attn_sinks else 0)
 
 
 def _attn_tail(cfg, ws):
@@ -158,6 +175,23 @@ def _attn_tail(cfg, ws):
     at nb, nb + 1 or None, and the sinks (the last parameter) or None."""
     nb = _n_block_weights(cfg, ws)
     return nb, (tuple(ws[nb:nb + 2]) if cfg.qk_norm else None), (ws[-1] if cfg.attn_sinks else None)
+
+
+def _out_norm_index(cfg, ws):
+    """The index in ``ws`` of ``self_attn.out_norm.weight`` (``mlp.out_norm.weight`` follows it) under
+    ``cfg.sandwich_norm`` -- after the QK-norm pair, before the sinks -- else None."""
+    if not cfg.sandwich_norm:
+        return None
+    return _n_block_weights(cfg, ws) + (2 if cfg.qk_norm else 0)
+
+
+def _ffn_out_fwd(cfg, x1, m, w_ffn_out, seed):
+    """x2 and rstd_m: the FFN output ``m`` joins the residual stream, through its out-norm under ``cfg.sandwich_norm``
+    (``w_ffn_out``; the kernel's form without a second norm), else by the plain add (rstd_m None)."""
+    if w_ffn_out is None:
+        return F_.dropout(x1, m, 0.0, seed, 0), None
+    x2, _, rstd_m, _ = F_.sandwich_fwd(x1, m, w_ffn_out, None, cfg.norm_eps)
+    return x2, rstd_m
 
 
 def _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn):
@@ -299,7 +333,12 @@ class _LayerFn(torch.autograd.Function):
                                       1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds,
                                       sink=sink, softcap=cfg.attn_softcap)
         a = F_.linear_fwd(o, wo)
-        x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
+        jo = _out_norm_index(cfg, ws)            # sandwich norms: ws[jo] the attention site's, ws[jo + 1] the FFN's
+        if jo is None:
+            x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
+            rstd_a = None
+        else:                   # x1 = x + RMSNorm(a) and h2 = RMSNorm(x1) in one launch
+            x1, h2, rstd_a, rstd2 = F_.sandwich_fwd(x, a, ws[jo], w_post, cfg.norm_eps)
         ctx.moe = None
         router_losses = None
         if cfg.n_experts:       # top-k routed experts instead of the dense FFN; gu / hh are per expert, in ctx.moe
@@ -310,11 +349,15 @@ class _LayerFn(torch.autograd.Function):
         else:
             wgu, wd = ws[4:6]
             gu = F_.linear_fwd(h2, wgu)
-            hh = F_.swiglu_fwd(gu)
+            hh = F_.swiglu_fwd(gu, cfg.ffn_act)
             m = F_.linear_fwd(hh, wd)
-        x2 = F_.dropout(x1, m, 0.0, rt.seed, 0)
+        x2, rstd_m = _ffn_out_fwd(cfg, x1, m, None if jo is None else ws[jo + 1], rt.seed)
         rt.release_forward(unit)
         ctx.model, ctx.i = model, i
+        # sandwich norms: the two sublayer outputs and their row statistics; "full" rebuilds a (and with it rstd_a)
+        ctx.sand = None
+        if jo is not None:
+            ctx.sand = (None, None, m, rstd_m) if ctx.recompute == "full" else (a, rstd_a, m, rstd_m)
         # raw: the q|k columns before QK-norm (None without it)
         ctx.saved = (x, h1, rstd1, qkv, o, lse, aux, x1, h2, rstd2, gu, hh, raw)
         if ctx.recompute == "selective":      # the backward rebuilds h1, h2 (norm_apply) and hh (swiglu_bwd_h)
@@ -340,21 +383,32 @@ class _LayerFn(torch.autograd.Function):
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
         dx2 = dx2.contiguous()
         s = [rt.grad_slot(unit, j) for j in range(len(ws))]
+        shared = rt.grad_reducer()
+        red = shared if shared is not None else F_.GradReducer()
+        jo = _out_norm_index(cfg, ws)
+        dm = dx2                # the gradient of the FFN output m: through the FFN site's out-norm under sandwich norms
+        if jo is not None:
+            a, rstd_a, m, rstd_m = ctx.sand
+            ctx.sand = None
+            dm = F_.norm_bwd(dx2, m, ws[jo + 1], None, rstd_m, None, s[jo + 1][0], None, s[jo + 1][1], True, red=red)
+            del m
         if ctx.moe is not None:
-            dh2 = _moe_bwd(model, unit, dx2, h2, ws[:nb], s[:nb], ctx.moe, daux)
+            dh2 = _moe_bwd(model, unit, dm, h2, ws[:nb], s[:nb], ctx.moe, daux)
             ctx.moe = None
         else:
             wgu, wd = ws[4:6]
-            F_.linear_wgrad(dx2, hh, s[5][0], None, s[5][1])
-            dhh = F_.linear_dgrad(dx2, wd, rt.weight_t(unit, 5, wd))
-            dgu = F_.swiglu_bwd(dhh, gu)
+            F_.linear_wgrad(dm, hh, s[5][0], None, s[5][1])
+            dhh = F_.linear_dgrad(dm, wd, rt.weight_t(unit, 5, wd))
+            dgu = F_.swiglu_bwd(dhh, gu, cfg.ffn_act)
             F_.linear_wgrad(dgu, h2, s[4][0], None, s[4][1])
             dh2 = F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, 4, wgu))
-        shared = rt.grad_reducer()
-        red = shared if shared is not None else F_.GradReducer()
-        dx1 = F_.norm_bwd(dh2, x1, w_post, None, rstd2, dx2, s[3][0], None, s[3][1], True, red=red)
-        F_.linear_wgrad(dx1, o, s[2][0], None, s[2][1])
-        do = F_.linear_dgrad(dx1, wo, rt.weight_t(unit, 2, wo))
+        if jo is None:
+            dx1 = F_.norm_bwd(dh2, x1, w_post, None, rstd2, dx2, s[3][0], None, s[3][1], True, red=red)
+            da = dx1
+        else:                   # dx1 = dx2 + the pre-norm's backward, da = the attention site's out-norm backward of dx1
+            dx1, da = F_.sandwich_bwd(dh2, x1, w_post, rstd2, dx2, a, ws[jo], rstd_a, s[3], s[jo], red)
+        F_.linear_wgrad(da, o, s[2][0], None, s[2][1])
+        do = F_.linear_dgrad(da, wo, rt.weight_t(unit, 2, wo))
         qd, kd = Hq * D, Hkv * D
         dqkv = torch.empty_like(qkv)
         window = 0 if ctx.bounds is not None else cfg.sliding_window or 0
@@ -412,7 +466,7 @@ def _moe_fwd(model, i, h2, ws):
     for e in range(E):
         rows = slice(e * C, (e + 1) * C)
         gu = F_.linear_fwd(xe[rows], ws[1 + 2 * e])
-        hh = F_.swiglu_fwd(gu)
+        hh = F_.swiglu_fwd(gu, cfg.ffn_act)
         ye[rows].copy_(F_.linear_fwd(hh, ws[2 + 2 * e]))
         gus.append(gu)
         hhs.append(hh)
@@ -440,7 +494,7 @@ def _moe_bwd(model, unit, dm, h2, ws, s, saved, daux=None):
         F_.moe_aux_bwd_(dlogits, logits, lse, counts, g, model.cfg.moe_top_k)
         del logits, lse, counts
     if model.cfg.moe_dropless:
-        dxe = _moe_experts_bwd_dropless(rt, unit, dye, ws, s, saved)
+        dxe = _moe_experts_bwd_dropless(rt, unit, dye, ws, s, saved, model.cfg.ffn_act)
         F_.moe_router_wgrad(dlogits, h2, s[4][0], s[4][1], dense=dense)
         return F_.moe_dispatch_bwd(dxe, slot, dlogits, ws[4])
     dxe = torch.empty_like(xe)
@@ -450,7 +504,7 @@ def _moe_bwd(model, unit, dm, h2, ws, s, saved, daux=None):
         wgu, wd = ws[ju], ws[jd]
         F_.linear_wgrad(dye[rows], hhs[e], s[jd][0], None, s[jd][1])
         dhh = F_.linear_dgrad(dye[rows], wd, rt.weight_t(unit, jd, wd))
-        dgu = F_.swiglu_bwd(dhh, gus[e])
+        dgu = F_.swiglu_bwd(dhh, gus[e], model.cfg.ffn_act)
         gus[e] = hhs[e] = None
         F_.linear_wgrad(dgu, xe[rows], s[ju][0], None, s[ju][1])
         dxe[rows].copy_(F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, ju, wgu)))
@@ -479,7 +533,7 @@ def _moe_fwd_dropless(model, i, h2, ws):
     del logits
     xe = F_.moe_dispatch(h2, src)
     gu = F_.gemm_grouped_nt(xe, offsets, [ws[1 + 2 * e] for e in range(E)])
-    hh = F_.swiglu_fwd(gu)
+    hh = F_.swiglu_fwd(gu, cfg.ffn_act)
     ye = F_.gemm_grouped_nt(hh, offsets, [ws[2 + 2 * e] for e in range(E)])
     m = F_.moe_combine(ye, slot, gate)
     saved = (expert, gate, slot, src, xe, ye, gu, hh, offsets) + extra
@@ -500,7 +554,7 @@ def _moe_weights_t(rt, unit, ws, js):
     return list(buf)
 
 
-def _moe_experts_bwd_dropless(rt, unit, dye, ws, s, saved):
+def _moe_experts_bwd_dropless(rt, unit, dye, ws, s, saved, act="swiglu"):
     """The experts' part of :func:`_moe_bwd` on the packed layout: two grouped TN products write every expert's two
     weight gradients into their slots (an expert without rows gets exact zeros, or keeps its slot when accumulating)
     and two grouped NT products on W^T give the data gradients -- four launches instead of 4 E GEMM calls and 2 E
@@ -510,7 +564,7 @@ def _moe_experts_bwd_dropless(rt, unit, dye, ws, s, saved):
     ju, jd = [5 + 2 * e for e in range(E)], [6 + 2 * e for e in range(E)]
     F_.gemm_grouped_tn(dye, hh, offsets, [s[j][0] for j in jd], [s[j][1] for j in jd])
     dhh = F_.gemm_grouped_nt(dye, offsets, _moe_weights_t(rt, unit, ws, jd))
-    dgu = F_.swiglu_bwd(dhh, gu)
+    dgu = F_.swiglu_bwd(dhh, gu, act)
     del dhh
     F_.gemm_grouped_tn(dgu, xe, offsets, [s[j][0] for j in ju], [s[j][1] for j in ju])
     return F_.gemm_grouped_nt(dgu, offsets, _moe_weights_t(rt, unit, ws, ju))
@@ -533,6 +587,8 @@ def _layer_backward_recompute(ctx, dx2):
     * with QK-norm both modes treat ``raw`` like qkv: ``selective`` keeps it, ``full`` rebuilds it with qkv.
     * attention sinks keep nothing more in either mode: the kept o and lse already include the sink; nor does
       ``attn_softcap`` (the kept lse is that of the capped scores).
+    * sandwich norms: both modes also hold the FFN output m and its rstd row (the down projection is never re-run);
+      ``selective`` keeps a and its rstd row too, ``full`` rebuilds them with x1 / h2 / rstd2 (``sandwich_fwd``).
     * ``full`` kept x, o, lse.  The MLP half (a = o Wo^T, x1 / h2 / rstd2, gu) is rebuilt first and the attention
       half (h1 / rstd1, qkv + RoPE, under context parallelism the gathered K | V) only when the MLP half has been
       consumed and freed, so the rebuilt working set is half a layer's.  Attention itself and the down projection
@@ -556,29 +612,46 @@ def _layer_backward_recompute(ctx, dx2):
     dx2 = dx2.contiguous()
     s = [rt.grad_slot(unit, j) for j in range(len(ws))]
     sq, sk = (s[nb], s[nb + 1]) if qkn else (None, None)
+    shared = rt.grad_reducer()
+    red = shared if shared is not None else F_.GradReducer()
+    jo = _out_norm_index(cfg, ws)
+    a = rstd_a = None
+    if jo is not None:
+        a, rstd_a, m, rstd_m = ctx.sand
+        ctx.sand = None
     # ---- MLP half
     if full:
         a = F_.linear_fwd(o, wo)
-        x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
-        del a
+        if jo is None:
+            x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
+            a = None
+        else:
+            x1, h2, rstd_a, rstd2 = F_.sandwich_fwd(x, a, ws[jo], w_post, cfg.norm_eps)
         gu = F_.linear_fwd(h2, wgu)
     else:
         h2 = F_.norm_apply(x1, w_post, None, None, rstd2, True)
-    dhh = F_.linear_dgrad(dx2, wd, rt.weight_t(unit, 5, wd))
-    dgu, hh = F_.swiglu_bwd_h(dhh, gu)
+    dm = dx2
+    if jo is not None:
+        dm = F_.norm_bwd(dx2, m, ws[jo + 1], None, rstd_m, None, s[jo + 1][0], None, s[jo + 1][1], True, red=red)
+        del m, rstd_m
+    dhh = F_.linear_dgrad(dm, wd, rt.weight_t(unit, 5, wd))
+    dgu, hh = F_.swiglu_bwd_h(dhh, gu, cfg.ffn_act)
     del dhh, gu
-    F_.linear_wgrad(dx2, hh, s[5][0], None, s[5][1])
-    del hh
+    F_.linear_wgrad(dm, hh, s[5][0], None, s[5][1])
+    del hh, dm
     F_.linear_wgrad(dgu, h2, s[4][0], None, s[4][1])
     del h2
     dh2 = F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, 4, wgu))
     del dgu
-    shared = rt.grad_reducer()
-    red = shared if shared is not None else F_.GradReducer()
-    dx1 = F_.norm_bwd(dh2, x1, w_post, None, rstd2, dx2, s[3][0], None, s[3][1], True, red=red)
-    del dh2, x1, rstd2, dx2
-    F_.linear_wgrad(dx1, o, s[2][0], None, s[2][1])
-    do = F_.linear_dgrad(dx1, wo, rt.weight_t(unit, 2, wo))
+    if jo is None:
+        dx1 = F_.norm_bwd(dh2, x1, w_post, None, rstd2, dx2, s[3][0], None, s[3][1], True, red=red)
+        da = dx1
+    else:
+        dx1, da = F_.sandwich_bwd(dh2, x1, w_post, rstd2, dx2, a, ws[jo], rstd_a, s[3], s[jo], red)
+    del dh2, x1, rstd2, dx2, a, rstd_a
+    F_.linear_wgrad(da, o, s[2][0], None, s[2][1])
+    do = F_.linear_dgrad(da, wo, rt.weight_t(unit, 2, wo))
+    del da
     # ---- attention half
     window = 0 if ctx.bounds is not None else cfg.sliding_window or 0
     if full:

@@ -90,7 +90,7 @@ def _moe_ffn(mlp, h, cfg):
     ys = []
     for e, ex in enumerate(mlp.experts):
         g, u = ex.gate_up_proj(xe[e * C:(e + 1) * C]).chunk(2, -1)
-        ys.append(ex.down_proj(F.silu(g) * u))
+        ys.append(ex.down_proj(_glu_act(g, cfg) * u))
     ye = torch.cat(ys, 0)
     out = torch.zeros_like(h)
     for k in range(K):
@@ -112,6 +112,16 @@ def _moe_aux_loss(mlp, h, cfg):
     balance = E * (f * torch.softmax(logits, -1).mean(0)).sum()
     z = torch.logsumexp(logits, -1).pow(2).mean()
     return cfg.moe_aux_loss_coef * balance + cfg.moe_z_loss_coef * z
+
+
+def _glu_act(g, cfg):
+    """The gated FFN's activation of the gate: SiLU, or the tanh form of GELU under ``cfg.ffn_act = "geglu"``."""
+    return F.gelu(g, approximate="tanh") if cfg.ffn_act == "geglu" else F.silu(g)
+
+
+def _out(sub, y):
+    """A sublayer's output on its way into the residual stream: through ``sub.out_norm`` under ``cfg.sandwich_norm``."""
+    return sub.out_norm(y) if hasattr(sub, "out_norm") else y
 
 
 class OracleMistral(nn.Module):
@@ -138,6 +148,9 @@ class OracleMistral(nn.Module):
                 layer.self_attn.sinks = nn.Parameter(torch.zeros(cfg.n_head))
             layer.post_attention_layernorm = _RMSNorm(d, cfg.norm_eps)
             layer.mlp = nn.Module()
+            if cfg.sandwich_norm:   # every sublayer's output through its own RMSNorm before the residual add
+                layer.self_attn.out_norm = _RMSNorm(d, cfg.norm_eps)
+                layer.mlp.out_norm = _RMSNorm(d, cfg.norm_eps)
             if cfg.n_experts:       # mixture of experts: a router and n_experts FFNs (autograd only, _moe_ffn)
                 layer.mlp.router = nn.Linear(d, cfg.n_experts, bias=False)
                 layer.mlp.experts = nn.ModuleList()
@@ -200,16 +213,16 @@ class OracleMistral(nn.Module):
                     o = F.scaled_dot_product_attention(q, k, v, attn_mask=band)
             else:
                 o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-            x = x + layer.self_attn.o_proj(o.transpose(1, 2).reshape(B, T, H * hd))
+            x = x + _out(layer.self_attn, layer.self_attn.o_proj(o.transpose(1, 2).reshape(B, T, H * hd)))
             if cfg.n_experts:
                 h2 = layer.post_attention_layernorm(x).reshape(B * T, -1)
                 if cfg.moe_aux_loss_coef or cfg.moe_z_loss_coef:
                     aux.append(_moe_aux_loss(layer.mlp, h2, cfg))
-                x = x + _moe_ffn(layer.mlp, h2, cfg).view_as(x)
+                x = x + _out(layer.mlp, _moe_ffn(layer.mlp, h2, cfg).view_as(x))
                 continue
             gu = layer.mlp.gate_up_proj(layer.post_attention_layernorm(x))
             g, u = gu.chunk(2, -1)
-            x = x + layer.mlp.down_proj(F.silu(g) * u)
+            x = x + _out(layer.mlp, layer.mlp.down_proj(_glu_act(g, cfg) * u))
         logits = self.lm_head(self.model.norm(x))
         if cfg.final_softcap:       # final-logit soft-capping: the loss and the returned logits are the capped ones
             logits = cfg.final_softcap * torch.tanh(logits / cfg.final_softcap)

@@ -193,6 +193,43 @@ def norm_bwd(dy, s, w, mean, rstd, dres, gw, gb, accumulate, rms, red=None, bias
     return ref.norm_bwd(dy, s, w, mean, rstd, dres, gw, gb, accumulate, rms)
 
 
+def sandwich_fwd(x, a, w_out, w_next, eps):
+    """Sandwich norm, "normalise, then add" (csrc/sandwich_norm.hip; definition: ref.py ``sandwich_fwd``):
+    s = x + RMSNorm(a; w_out) and, with ``w_next``, y = RMSNorm(s; w_next) of the stored s, in one launch.
+    Returns (s, y | None, rstd_a, rstd_s | None).  :func:`norm_apply` (s, w_next, rstd_s) rebuilds y bit for bit."""
+    if _gpu(x):
+        s, y, rstd_a, rstd_s = ext().sandwich_fwd(x, a, w_out, w_next, eps)
+        return (s, y, rstd_a, rstd_s) if w_next is not None else (s, None, rstd_a, None)
+    return ref.sandwich_fwd(x, a, w_out, w_next, eps)
+
+
+def sandwich_bwd_fused(like):
+    """Whether :func:`sandwich_bwd` runs its one-launch kernel for rows like ``like``'s: on the GPU at
+    d <= 2048; wider rows (and the CPU) compose two :func:`norm_bwd`."""
+    return _gpu(like) and ext().sandwich_bwd_supported(like.shape[-1])
+
+
+def sandwich_bwd(dy, s, w_next, rstd_s, dres, a, w_out, rstd_a, g_next, g_out, red):
+    """The backward of :func:`sandwich_fwd` with ``w_next``: dx = dres + RMSNormBwd(dy; s, w_next, rstd_s) and
+    da = RMSNormBwd(dx; a, w_out, rstd_a) of the stored dx.  Returns (dx, da).  ``g_next`` / ``g_out``: the
+    (slot, accumulate) pairs of the two weight gradients, whose fp32 partials reach them through ``red`` (a
+    :class:`GradReducer`; on the CPU at once).  One launch where the row fits the fused kernel
+    (:func:`sandwich_bwd_fused`), else the two :func:`norm_bwd` calls, which obey the same contract."""
+    if sandwich_bwd_fused(dy):
+        dx, da, part = ext().sandwich_bwd(dy, s, w_next, rstd_s, dres, a, w_out, rstd_a)
+        red.add(part[0], g_next[0], g_next[1])
+        red.add(part[1], g_out[0], g_out[1])
+        return dx, da
+    if not _gpu(dy):
+        dx, da, part = ref.sandwich_bwd(dy, s, w_next, rstd_s, dres, a, w_out, rstd_a)
+        reduce_partials(red, part[0], g_next[0], g_next[1])
+        reduce_partials(red, part[1], g_out[0], g_out[1])
+        return dx, da
+    dx = norm_bwd(dy, s, w_next, None, rstd_s, dres, g_next[0], None, g_next[1], True, red=red)
+    da = norm_bwd(dx, a, w_out, None, rstd_a, None, g_out[0], None, g_out[1], True, red=red)
+    return dx, da
+
+
 # ------------------------------------------------------------------------------ elementwise
 def gelu_fwd(f, out=None):
     return ext().gelu_fwd(f, out) if _gpu(f) else _into(out, ref.gelu_fwd(f))
@@ -359,21 +396,29 @@ def dropout(x, r, p, seed, site):
     return ref.dropout(x, r, p, seed, site)
 
 
-def swiglu_fwd(gu):
-    return ext().swiglu_fwd(gu) if _gpu(gu) else ref.swiglu_fwd(gu)
+def swiglu_fwd(gu, act="silu"):
+    """h = silu(gate) * up of gu = [gate | up]; ``act="geglu"``: gelu_tanh(gate) * up (ref.py ``swiglu_fwd``)."""
+    geglu = ref.glu_is_geglu(act)
+    if not _gpu(gu):
+        return ref.swiglu_fwd(gu, act)
+    return ext().swiglu_fwd(gu, True) if geglu else ext().swiglu_fwd(gu)
 
 
-def swiglu_bwd(dh, gu):
-    return ext().swiglu_bwd(dh, gu) if _gpu(dh) else ref.swiglu_bwd(dh, gu)
+def swiglu_bwd(dh, gu, act="silu"):
+    geglu = ref.glu_is_geglu(act)
+    if not _gpu(dh):
+        return ref.swiglu_bwd(dh, gu, act)
+    return ext().swiglu_bwd(dh, gu, True) if geglu else ext().swiglu_bwd(dh, gu)
 
 
-def swiglu_bwd_h(dh, gu):
+def swiglu_bwd_h(dh, gu, act="silu"):
     """(dgu, h) = (swiglu_bwd(dh, gu), swiglu_fwd(gu)), both bit for bit, from one pass over ``gu`` and ``dh``
     (csrc/elementwise.hip swiglu_bwd_h_kernel): the SwiGLU backward of a forward that did not keep h."""
+    geglu = ref.glu_is_geglu(act)
     if _gpu(dh):
-        dgu, h = ext().swiglu_bwd_h(dh, gu)
+        dgu, h = ext().swiglu_bwd_h(dh, gu, True) if geglu else ext().swiglu_bwd_h(dh, gu)
         return dgu, h
-    return ref.swiglu_bwd_h(dh, gu)
+    return ref.swiglu_bwd_h(dh, gu, act)
 
 
 # ------------------------------------------------------------------------------ mixture of experts

@@ -97,6 +97,33 @@ def norm_bwd(dy, s, w, mean, rstd, dres, gw, gb, accumulate, rms):
     return dx.to(dy.dtype).view_as(dy)
 
 
+def sandwich_fwd(x, a, w_out, w_next, eps):
+    """Sandwich norm, "normalise, then add": rstd_a = rsqrt(mean(a^2) + eps), s = round16(x + a rstd_a w_out) -- the
+    normalised value is never rounded on its own -- and, with ``w_next``, rstd_s and y = round16(s rstd_s w_next) from
+    the STORED s, as :func:`norm_fwd` forms them.  Returns (s, y | None, rstd_a, rstd_s | None)."""
+    dt = x.dtype
+    a32 = _f(a)
+    rstd_a = torch.rsqrt(a32.pow(2).mean(-1, keepdim=True) + eps)
+    s = (_f(x) + a32 * rstd_a * _f(w_out)).to(dt)
+    if w_next is None:
+        return s, None, rstd_a.reshape(-1), None
+    s32 = _f(s)
+    rstd_s = torch.rsqrt(s32.pow(2).mean(-1, keepdim=True) + eps)
+    return s, (s32 * rstd_s * _f(w_next)).to(dt), rstd_a.reshape(-1), rstd_s.reshape(-1)
+
+
+def sandwich_bwd(dy, s, w_next, rstd_s, dres, a, w_out, rstd_a):
+    """The backward of :func:`sandwich_fwd` with ``w_next``: ds = dres + RMSNormBwd(dy; s, w_next, rstd_s),
+    dx = round16(ds), da = round16(RMSNormBwd(dx; a, w_out, rstd_a)) from the STORED dx -- two :func:`norm_bwd` in a
+    row.  Returns (dx, da, part) with part fp32 [2, 1, d]: the sums over the rows of dy s rstd_s (gradient of
+    ``w_next``) and of dx a rstd_a (gradient of ``w_out``); the GPU kernel returns one row per workgroup."""
+    d = dy.shape[-1]
+    part = torch.zeros(2, 1, d, dtype=torch.float32, device=dy.device)
+    dx = norm_bwd(dy, s, w_next, None, rstd_s, dres, part[0, 0], None, False, True)
+    da = norm_bwd(dx, a, w_out, None, rstd_a, None, part[1, 0], None, False, True)
+    return dx, da, part
+
+
 # ------------------------------------------------------------------------------ elementwise
 def gelu_fwd(f):
     return F.gelu(_f(f)).to(f.dtype)
@@ -123,25 +150,55 @@ def dropout(x, r, p, seed, site):
     return out.to(r.dtype)
 
 
-def swiglu_fwd(gu):
+GLU_ACTS = {"silu": False, "swiglu": False, "geglu": True}      # name -> the gate's activation is gelu_tanh
+
+
+def glu_is_geglu(act):
+    """True for the GeGLU FFN (``"geglu"``), False for SwiGLU (``"silu"`` or the config's ``"swiglu"``)."""
+    if act not in GLU_ACTS:
+        raise ValueError(f"the gated FFN's activation must be one of {', '.join(GLU_ACTS)}, got {act!r}")
+    return GLU_ACTS[act]
+
+
+_GELU_K, _GELU_C = math.sqrt(2.0 / math.pi), 0.044715
+
+
+def _gelu_tanh_parts(g):
+    """(hp, grad) with gelu_tanh(g) = g hp: hp = 0.5 (1 + t), t = tanh(k (g + c g^3)); grad = d gelu_tanh / dg =
+    hp + 0.5 g (1 - t^2) k (1 + 3 c g^2), the second term exactly 0 where t = +-1 (0 * inf once g^2 overflows)."""
+    g2 = g * g
+    t = torch.tanh(_GELU_K * (g * (1.0 + _GELU_C * g2)))
+    hp = 0.5 * (1.0 + t)
+    q = 1.0 - t * t
+    second = torch.where(q == 0, torch.zeros_like(g), 0.5 * g * q * (_GELU_K * (1.0 + 3.0 * _GELU_C * g2)))
+    return hp, hp + second
+
+
+def swiglu_fwd(gu, act="silu"):
+    """h = silu(gate) * up; ``act="geglu"``: h = gelu_tanh(gate) * up (the Gemma FFN)."""
     F2 = gu.shape[-1] // 2
     g, u = _f(gu)[..., :F2], _f(gu)[..., F2:]
+    if glu_is_geglu(act):
+        return (g * _gelu_tanh_parts(g)[0] * u).to(gu.dtype)
     return (F.silu(g) * u).to(gu.dtype)
 
 
-def swiglu_bwd(dh, gu):
+def swiglu_bwd(dh, gu, act="silu"):
     F2 = gu.shape[-1] // 2
     g, u = _f(gu)[..., :F2], _f(gu)[..., F2:]
-    s = torch.sigmoid(g)
     d = _f(dh)
+    if glu_is_geglu(act):
+        hp, grad = _gelu_tanh_parts(g)
+        return torch.cat([d * grad * u, d * (g * hp)], -1).to(gu.dtype)
+    s = torch.sigmoid(g)
     dg = d * u * s * (1 + g * (1 - s))
     du = d * g * s
     return torch.cat([dg, du], -1).to(gu.dtype)
 
 
-def swiglu_bwd_h(dh, gu):
+def swiglu_bwd_h(dh, gu, act="silu"):
     """(dgu, h): :func:`swiglu_bwd` and the forward's h = :func:`swiglu_fwd` (gu), which the forward did not keep."""
-    return swiglu_bwd(dh, gu), swiglu_fwd(gu)
+    return swiglu_bwd(dh, gu, act), swiglu_fwd(gu, act)
 
 
 def rope_tables(T, D, theta, device=None):

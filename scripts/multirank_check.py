@@ -25,7 +25,7 @@ ranks (dltb/parallel/context.py): the ranks of a group read the same rows, and t
 world-1 run trains.  Its Mistral-shape cases (``CP_CASES``: every strategy, a sliding window, packed documents)
 are not part of the default ``--cases``.  ``--activation-recompute`` sets the Mistral-shape cases' saved set; a run
 with it must train the model the ``off`` run trains; so must one with ``--head-chunk N`` (the Mistral-shape cases' LM
-head in chunks of N rows).  ``--qk-norm`` turns QK-norm on in the Mistral-shape cases, ``--attn-sinks`` the learned attention sinks, ``--attn-softcap C`` the attention logit soft-capping, ``--final-softcap C`` / ``--lm-z-loss-coef B`` the head-loss options.  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
+head in chunks of N rows).  ``--qk-norm`` turns QK-norm on in the Mistral-shape cases, ``--attn-sinks`` the learned attention sinks, ``--attn-softcap C`` the attention logit soft-capping, ``--final-softcap C`` / ``--lm-z-loss-coef B`` the head-loss options, ``--sandwich-norm`` / ``--ffn-act geglu`` the sandwich norms and the GeGLU FFN.  Reference semantics being checked: train_harness.py:210-271 (DDP / FSDP /
 DeepSpeed ZeRO-2/3 wrap) -- at any world size the trained model must be the one the global batch
 defines.
 """
@@ -111,6 +111,8 @@ def run_case(name, spec, world, rank, device, a):
         mcfg.moe_dropless = a.moe_dropless
     if a.qk_norm and mcfg.arch == "mistral":                      # the Mistral-shape cases only
         mcfg.qk_norm = True
+    if mcfg.arch == "mistral":                                    # the Mistral-shape cases only
+        mcfg.sandwich_norm, mcfg.ffn_act = a.sandwich_norm, a.ffn_act
     if a.attn_sinks and mcfg.arch == "mistral":                   # the Mistral-shape cases only
         mcfg.attn_sinks = True
     if a.attn_softcap and mcfg.arch == "mistral":                 # the Mistral-shape cases only
@@ -205,6 +207,10 @@ def main():
     ap.add_argument("--moe-dropless", action="store_true", help="with --moe-experts: the dropless grouped-GEMM path")
     ap.add_argument("--qk-norm", action="store_true",
                     help="QK-norm fused with RoPE in the Mistral-shape cases (models/mistral.py)")
+    ap.add_argument("--sandwich-norm", action="store_true",
+                    help="sandwich norms in the Mistral-shape cases (models/mistral.py)")
+    ap.add_argument("--ffn-act", choices=["swiglu", "geglu"], default="swiglu",
+                    help="the gated FFN's activation in the Mistral-shape cases (models/mistral.py)")
     ap.add_argument("--attn-sinks", action="store_true",
                     help="learned attention sinks in the Mistral-shape cases (models/mistral.py)")
     ap.add_argument("--attn-softcap", type=float, default=0.0,
