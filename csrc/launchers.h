@@ -304,6 +304,35 @@ int dltb_gemm_rs_bm(int cfg);
 // C = (A B^T) * aux (elementwise, rounded once) with per-m-tile fp32 column partials of C (the dGELU epilogue)
 bool dltb_gemm_rs_aux_supported(int M, int N, int K, int cfg);
 
+// ---- muon.hip: the Muon optimizer (momentum -> Newton-Schulz -> update), bf16 work buffers, fp32 accumulation.
+// Batched products over stacked same-shape matrices (row strides ld*, batch strides s*, in elements); the final
+// scale is alpha * dalpha[batch * dalpha_stride] (dalpha: optional per-batch device scalars).
+//   syrk:  C[m,m] = alpha X X^T + beta D; X [m][k], D optional symmetric [m][m]; lower-triangle tiles of bt x bt
+//          (bt 64 | 128, 0 = by shape), both triangles written from the same accumulator.  Returns bt, -1 for an
+//          unsupported shape / layout, -2 when C overlaps X or D
+//   apply: Y[m,n] = alpha (a X + B X); B [m][m], X [m][n]; cfg 0 = 128x128, 1 = 128x64, 2 = 64x128, 3 = 64x64
+//          (BM x BN), -1 = by shape.  Returns cfg, -1 unsupported, -2 when Y overlaps X or B
+bool dltb_muon_syrk_supported(int m, int k, int batch, int bt);
+int dltb_muon_syrk(const void* x, const void* d, void* c, long ldx, long ldd, long ldc, long sx, long sd, long sc,
+                   int m, int k, int batch, float alpha, float beta, const float* dalpha, long dalpha_stride, int bt,
+                   hipStream_t st);
+bool dltb_muon_apply_supported(int m, int n, int batch, int cfg);
+int dltb_muon_apply(const void* b, const void* x, void* y, long ldb, long ldx, long ldy, long sb, long sx, long sy,
+                    int m, int n, int batch, float alpha, float a, const float* dalpha, long dalpha_stride, int cfg,
+                    hipStream_t st);
+// mat_tab: 8 int64 per matrix (rows, cols, owner offset, momentum offset, work offset, 16-bit destination pointer,
+// first block row, block count); blk_mat / blk_tile: one row per 64 x 64 tile of a matrix as stored.
+//   momentum: mom = mu mom + gs g, U = bf16(gs g + mu mom) (transposed where rows > cols), partial[block] = sum U^2,
+//             norms[2 i] = 1 / (sqrt(sum U_i^2) + eps), norms[2 i + 1] = its square (fixed summation order)
+//   update:   W -= lr (0.2 sqrt(max(rows, cols)) O + wd W) on the fp32 master and its 16-bit copy; lr = hp[0] if hp
+// both return at once when hp[3] != 0 (a skipped step)
+bool dltb_muon_matrix_supported(long rows, long cols);
+void dltb_muon_momentum(const void* grad, bool grad_bf16, float* mom, void* U, float* partial, float* norms,
+                        const int64_t* mat_tab, int nmat, const int* blk_mat, const int* blk_tile, int nblocks,
+                        const float* gscale, const float* hp, float mu, float eps, hipStream_t st);
+void dltb_muon_update(float* master, const void* O, const int64_t* mat_tab, const int* blk_mat, const int* blk_tile,
+                      int nblocks, const float* hp, float lr, float wd, hipStream_t st);
+
 // device-scalar helpers (head backward: no host sync)
 void dltb_xent_mean(const float* loss, const int64_t* targets, int N, int64_t ignore_index, float* out,
                     hipStream_t st);

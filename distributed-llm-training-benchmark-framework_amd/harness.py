@@ -156,6 +156,11 @@ def build_parser():
                         "and for sqrt(exp_avg_sq), one fp32 power-of-two scale per 256 elements, stochastic "
                         "rounding): 6 bytes of optimizer state per parameter instead of 12; master weights stay "
                         "fp32; every strategy and tier")
+    p.add_argument("--optimizer", choices=["adamw", "muon"], default="adamw",
+                   help="adamw, or muon = Muon (Nesterov momentum orthogonalised by five Newton-Schulz steps on "
+                        "symmetric MFMA GEMMs) on the transformer blocks' matrices and AdamW on everything else; "
+                        "bf16, DDP at any world size, ZeRO-1/2 at world size 1")
+    p.add_argument("--muon-momentum", type=float, default=0.95, help="Muon's momentum coefficient")
     p.add_argument("--grad-comm-dtype", choices=["auto", "bf16", "fp16", "fp32"], default="auto",
                    help="DDP gradient all-reduce dtype: the compute dtype or fp32; auto = fp32 when DDP "
                         "runs the reference's fp16 path (torch DDP reduces fp32 grads), else the compute dtype")
@@ -214,7 +219,9 @@ def _engine_for(args, model, device):
     cfg = engine_config(args.strategy, args.grad_accum, args.accum_semantics, ds, fc,
                         compute_dtype=DTYPES[args.dtype], bucket_mb=args.bucket_mb, seed=args.seed,
                         grad_reduce=getattr(args, "grad_reduce", "micro"),
-                        optimizer_state=getattr(args, "optimizer_state", "fp32"))
+                        optimizer_state=getattr(args, "optimizer_state", "fp32"),
+                        optimizer=getattr(args, "optimizer", "adamw"),
+                        muon_momentum=getattr(args, "muon_momentum", 0.95))
     cfg.extra["grad_comm_dtype"] = "fp32" if getattr(args, "grad_comm_dtype", None) == "fp32" else "compute"
     if args.strategy == "ddp" and getattr(args, "ddp_shard_optimizer", False):
         cfg.extra["shard_optimizer"] = True       # DDP + ZeroRedundancyOptimizer (parallel/replicated.py)
@@ -512,6 +519,9 @@ def train(args):
         if getattr(args, "optimizer_state", "fp32") == "fp8" and is_main:
             print("optimizer state: AdamW moments as block-scaled FP8 (E4M3) codes, stochastically rounded; master "
                   "weights fp32", flush=True)
+        if getattr(args, "optimizer", "adamw") == "muon" and is_main:
+            print(f"optimizer: Muon (momentum {args.muon_momentum:g}, 5 Newton-Schulz steps) on the blocks' matrices, "
+                  "AdamW on the rest", flush=True)
         if mcfg.lm_z_loss_coef and is_main:
             print(f"LM-head z-loss: {mcfg.lm_z_loss_coef:g} * mean(logsumexp(logits)^2) over the valid rows, included "
                   "in the reported loss", flush=True)
@@ -677,6 +687,8 @@ def train(args):
             "final_softcap": float(mcfg.final_softcap),
             "lm_z_loss_coef": float(mcfg.lm_z_loss_coef),
             "optimizer_state": engine.opt.state, "optimizer_bytes": engine.opt.state_bytes,
+            "optimizer": ecfg.optimizer, "muon_momentum": ecfg.muon_momentum if ecfg.optimizer == "muon" else None,
+            "muon_matrices": len(engine.opt.matrices) if ecfg.optimizer == "muon" else 0,
             # the last micro-step's assignments per layer and expert (before drops) and, with an auxiliary router
             # loss on, its per-layer values, read once, here
             "moe": model.moe_stats(head_rows) if mcfg.n_experts else None,

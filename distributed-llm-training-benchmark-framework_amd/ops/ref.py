@@ -877,3 +877,60 @@ def adamw_flat_fp8(master, mq, sq, mscale, sscale, grad, lr, beta1, beta2, eps, 
         c, sc = fp8_quantize(val, kind, seed, counter, owner_off, rounding)
         codes.copy_(c)
         scales.copy_(sc)
+
+
+# ---- Muon (csrc/muon.hip; optim/muon.py calls these on the CPU) -----------------------------------------------
+# Momentum -> Newton-Schulz orthogonalisation -> update, per matrix W [rows, cols].  The rounding points are part of
+# the contract: the Newton-Schulz operand and every product are bf16, accumulation is ``dtype`` (fp32 on the CPU
+# path, float64 in tests).  ``round=False`` drops the bf16 roundings: the exact chain.
+MUON_ABC = (3.4445, -4.7750, 2.0315)
+MUON_NS_STEPS = 5
+MUON_MOMENTUM = 0.95
+MUON_EPS = 1e-7
+
+
+def _bf16r(x, round=True):
+    return x.to(torch.bfloat16).to(x.dtype) if round else x
+
+
+def muon_momentum(mom, grad, mu=MUON_MOMENTUM, gscale=None, dtype=torch.float32, round=True):
+    """``mom = mu mom + gs g`` in place (``mom`` keeps its dtype); returns ``(U, s)``: ``U = bf16(gs g + mu mom)`` as
+    a ``dtype`` tensor, transposed when rows > cols so it is [m, n] with m <= n, and ``s = 1 / (sqrt(sum U^2) + eps)``
+    over the rounded U."""
+    g = grad.to(dtype)
+    if gscale is not None:
+        g = g * gscale.to(dtype)
+    m = mom.to(dtype) * mu + g
+    mom.copy_(m)
+    U = _bf16r(g + mu * m, round)
+    if U.shape[0] > U.shape[1]:
+        U = U.t().contiguous()
+    s = 1.0 / (U.pow(2).sum().sqrt() + MUON_EPS)
+    return U, s
+
+
+def muon_newton_schulz(U, s, steps=MUON_NS_STEPS, dtype=torch.float32, round=True):
+    """``steps`` quintic Newton-Schulz iterations on ``X0 = U`` [m, n], m <= n; the scale ``s`` is folded into the
+    first one:  A = bf16(s^2 X X^T);  B = bf16(b A + c A A);  X' = bf16(s (a X + B X)), and s = 1 afterwards."""
+    a, b, c = MUON_ABC
+    X = U.to(dtype)
+    sc = torch.as_tensor(s, dtype=dtype)
+    for i in range(steps):
+        A = _bf16r(sc * sc * (X @ X.t()), round)
+        B = _bf16r(b * A + c * (A @ A), round)
+        X = _bf16r(sc * (a * X + B @ X), round)
+        sc = torch.ones((), dtype=dtype)
+    return X
+
+
+def muon_update(master, O, lr, wd, dtype=torch.float32, round=True):
+    """``W -= lr (0.2 sqrt(max(rows, cols)) O + wd W)`` in place on ``master`` [rows, cols]; ``O`` is the last
+    Newton-Schulz iterate, read back through the transpose where :func:`muon_momentum` transposed.  The update has no
+    bf16 rounding point of its own (the compute-dtype copy is the caller's), so ``round`` changes nothing here; it is
+    taken so that the three functions share one signature."""
+    rows, cols = master.shape
+    O = O.to(dtype)
+    if rows > cols:
+        O = O.t()
+    w = master.to(dtype)
+    master.copy_(w - lr * (0.2 * math.sqrt(max(rows, cols)) * O + wd * w))

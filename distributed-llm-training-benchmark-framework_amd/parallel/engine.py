@@ -43,6 +43,10 @@ class EngineConfig:
     seed: int = 42
     # AdamW moments: "fp32", or "fp8" = block-scaled E4M3 codes with stochastic rounding (optim/adamw.py)
     optimizer_state: str = "fp32"
+    # "adamw", or "muon": Muon on the transformer blocks' matrices, AdamW on the rest (optim/muon.py)
+    optimizer: str = "adamw"
+    muon_momentum: float = 0.95
+    muon_ns_steps: int = 5
     # sharded engines
     reshard_after_forward: bool = True
     prefetch: int = 1                         # units gathered ahead (forward and backward)
@@ -89,6 +93,10 @@ class Engine(ParamRuntime):
         self._wt = {}            # (unit index, param index) -> (W view, W^T view of a stacked buffer)
         self._wt_stack = {}      # (param index, shape) -> [units, K, N] buffer of transposes
         self._wt_epoch = -1      # optimizer step the cached transposes belong to
+        if cfg.optimizer not in ("adamw", "muon"):
+            raise ValueError(f"optimizer must be adamw or muon, not {cfg.optimizer!r}")
+        if cfg.optimizer == "muon":
+            self._check_muon()
         model.rt = self
         self._setup()
 
@@ -118,6 +126,14 @@ class Engine(ParamRuntime):
 
     def _on_begin_micro(self):
         pass
+
+    def _check_muon(self):
+        """Engines whose owner space holds whole matrices override this (parallel/replicated.py)."""
+        if self.cfg.extra.get("sub_group_elems"):
+            raise ValueError("--optimizer muon is not supported with ZeRO-3 sub_group launches: a sub-group cuts the "
+                             "owner space at element counts, Newton-Schulz needs whole matrices")
+        raise ValueError(f"--optimizer muon is not supported by {type(self).__name__} (sharded parameters: FSDP, "
+                         "ZeRO-3): Newton-Schulz needs whole matrices on the rank")
 
     def _finish_backward(self):
         pass

@@ -37,6 +37,7 @@ import torch
 from ..ops import functional as F_
 from ..ops._ext import ext
 from ..optim.adamw import FlatAdamW
+from ..optim.muon import FlatMuon, muon_matrices
 from .ds_config import check_bucket_caps
 from .engine import Engine
 from .flat import ALIGN, owner_segments, plan_layout
@@ -182,8 +183,20 @@ class ReplicatedEngine(Engine):
             opt_segs = [(bk.start, bk.end - bk.start, self.flat_param[bk.start:bk.end]) for bk in L.buckets]
             assert sum(x[1] for x in opt_segs) == g_full.numel() == L.total
         del master_full
-        self.opt = FlatAdamW(master, opt_segs, cfg.lr, cfg.betas, cfg.eps, cfg.weight_decay,
-                             state=cfg.optimizer_state, seed=cfg.seed)
+        if cfg.optimizer == "muon":
+            # owner offset of a flat offset (stage 0: the same; stages 1-2 at world 1: the rank owns every chunk)
+            own = owner_segments(L, self.rank) if shard else [(0, L.total, 0)]
+            mats = []
+            for u, i, name, shape in muon_matrices(model):
+                s = L.slot(u, i)
+                o = next(os_ + s.offset - fs for os_, ln, fs in own if fs <= s.offset and s.offset + s.numel <= fs + ln)
+                mats.append((name, shape, o, self.flat_param[s.offset:s.offset + s.numel]))
+            self.opt = FlatMuon(master, opt_segs, mats, cfg.lr, cfg.betas, cfg.eps, cfg.weight_decay,
+                                momentum=cfg.muon_momentum, ns_steps=cfg.muon_ns_steps, state=cfg.optimizer_state,
+                                seed=cfg.seed)
+        else:
+            self.opt = FlatAdamW(master, opt_segs, cfg.lr, cfg.betas, cfg.eps, cfg.weight_decay,
+                                 state=cfg.optimizer_state, seed=cfg.seed)
         self._ag_pending = {}    # bucket -> async all-gather of updated parameters (deferred step)
         self._defer_opt = (self.stage >= 1 and self.world > 1 and self._overlap and
                            bool(cfg.extra.get("defer_opt", os.environ.get("DLTB_DEFER_OPT", "1") == "1")))
@@ -513,8 +526,18 @@ class ReplicatedEngine(Engine):
             return self.acc
         return self.rs_out if self.world > 1 else self.flat_grad
 
+    def _check_muon(self):
+        """Muon updates whole matrices from whole gradients: the rank's owner space must hold them."""
+        if self.scaler is not None:
+            raise ValueError("--optimizer muon does not support fp16 compute with dynamic loss scaling; use bf16")
+        if int(self.cfg.zero_stage) >= 1 and self.world > 1:
+            raise ValueError("--optimizer muon needs whole matrices in the rank's owner space: it runs under DDP at "
+                             "any world size and under ZeRO-1/2 (or a sharded DDP optimizer) at world size 1 only")
+
     def _ddp_pipe_wanted(self):
         cfg = self.cfg
+        if cfg.optimizer == "muon":      # the update needs whole gradients, after the last all-reduce
+            return False
         return (int(cfg.zero_stage) == 0 and self.world > 1 and bool(cfg.extra.get("overlap_comm", True))
                 and self.scaler is None and not cfg.grad_clip > 0 and not cfg.extra.get("track_grad_norm", False)
                 and bool(cfg.extra.get("ddp_opt_pipeline", True)))

@@ -51,13 +51,18 @@ def engine_config(strategy: str, grad_accum: int = 1, semantics: str = "referenc
                   ds_config: Optional[dict] = None, fsdp_config: Optional[dict] = None,
                   compute_dtype=torch.bfloat16, bucket_mb: float = 64.0, seed: int = 42,
                   overrides: Optional[dict] = None, grad_reduce: str = "micro",
-                  optimizer_state: str = "fp32") -> EngineConfig:
+                  optimizer_state: str = "fp32", optimizer: str = "adamw",
+                  muon_momentum: float = 0.95) -> EngineConfig:
     """``grad_reduce`` (ZeRO-2 only): ``micro`` reduce-scatters the gradients after every micro-step
     (DeepSpeed stage 2, configs/deepspeed/zero2.json); ``window`` accumulates them locally over the
     ``grad_accum`` window and reduce-scatters once, during the boundary micro-step's backward
     (ZeRO-1 communication: 1/grad_accum of the xGMI traffic).  Optimizer state stays sharded
     either way, and the engine's flat gradient buffer is full-size in both modes, so HBM is the
-    same.  ``optimizer_state``: ``fp32`` AdamW moments, or ``fp8`` (block-scaled E4M3 codes, optim/adamw.py)."""
+    same.  ``optimizer_state``: ``fp32`` AdamW moments, or ``fp8`` (block-scaled E4M3 codes, optim/adamw.py).
+    ``optimizer``: ``adamw``, or ``muon`` (optim/muon.py; the engines refuse it where the rank does not own whole
+    matrices)."""
+    if optimizer not in ("adamw", "muon"):
+        raise ValueError(f"optimizer must be adamw or muon, not {optimizer}")
     if optimizer_state not in ("fp32", "fp8"):
         raise ValueError(f"optimizer_state must be fp32 or fp8, not {optimizer_state}")
     if grad_reduce not in ("micro", "window"):
@@ -65,7 +70,7 @@ def engine_config(strategy: str, grad_accum: int = 1, semantics: str = "referenc
     if strategy not in STRATEGIES:
         raise ValueError(f"unknown strategy {strategy}")
     cfg = EngineConfig(strategy=strategy, compute_dtype=compute_dtype, bucket_mb=bucket_mb, seed=seed,
-                       optimizer_state=optimizer_state)
+                       optimizer_state=optimizer_state, optimizer=optimizer, muon_momentum=float(muon_momentum))
     ds = ds_config or {}
     zero_like = strategy in ("zero2", "zero3") or semantics == "uniform"
     if zero_like:

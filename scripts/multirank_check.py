@@ -142,7 +142,7 @@ def run_case(name, spec, world, rank, device, a):
     over.update(spec.get("over", {}))
     cfg = engine_config(spec["strategy"], a.accum, "uniform", None, fc, bucket_mb=a.bucket_mb,
                         overrides=over, grad_reduce=spec.get("grad_reduce", "micro"),
-                        optimizer_state=a.optimizer_state)
+                        optimizer_state=a.optimizer_state, optimizer=a.optimizer)
     cfg.extra["grad_comm_dtype"] = spec.get("grad_comm_dtype", "compute")
     cfg.extra.update(spec.get("extra", {}))
     eng = make_engine(model, cfg, device)
@@ -224,6 +224,9 @@ def main():
                          "parameters); default: the run's device")
     ap.add_argument("--optimizer-state", default="fp32", choices=["fp32", "fp8"],
                     help="AdamW moments of every case: fp32, or block-scaled FP8 codes (optim/adamw.py)")
+    ap.add_argument("--optimizer", default="adamw", choices=["adamw", "muon"],
+                    help="the optimizer of every case: adamw, or muon on the blocks' matrices (optim/muon.py); muon "
+                         "runs under the ddp cases at any world size and is refused by the sharded ones")
     a = ap.parse_args()
     from dltb.utils.dist import cleanup_distributed, setup_distributed
     world = int(os.environ.get("WORLD_SIZE", "1"))
