@@ -304,6 +304,21 @@ int dltb_gemm_rs_bm(int cfg);
 // C = (A B^T) * aux (elementwise, rounded once) with per-m-tile fp32 column partials of C (the dGELU epilogue)
 bool dltb_gemm_rs_aux_supported(int M, int N, int K, int cfg);
 
+// ---- gemm_fp8.hip: row-scaled FP8 (OCP E4M3) linear layers.
+//   quant: nb matrices x[R][K] (16-bit, row stride ldx, matrix stride xbs, in elements; 16-byte aligned rows,
+//          K % 8 == 0) -> contiguous codes q[nb][R][K] and scales s[nb][R] (s = 2^e, the smallest power of two with
+//          max|x| / s <= 448; 1 for a zero row; NaN, with zero codes, for a row holding an inf or a NaN)
+//   gemm:  c[M][N] = round16((sum_k dec(a[m][k]) dec(b[n][k])) * sa[m] * sb[n]); a [M][K], b [N][K] codes with row
+//          strides lda / ldb in bytes (multiples of 16), ldc in elements (multiple of 4), sb 16-byte aligned;
+//          M, N, K multiples of 128.  cfg 0 = 128 x 128, 1 = 256 x 128 (M % 256 == 0), -1 = by shape.  Returns the
+//          cfg used, -1 when refused
+void dltb_fp8_quant_rows(const void* x, uint8_t* q, float* s, int R, int K, int nb, long ldx, long xbs,
+                         hipStream_t st);
+bool dltb_gemm_fp8_supported(int M, int N, int K);
+int dltb_gemm_fp8_pick(int M, int N, int K);
+int dltb_gemm_fp8(const uint8_t* a, const float* sa, const uint8_t* b, const float* sb, void* c, long lda, long ldb,
+                  long ldc, int M, int N, int K, int cfg, hipStream_t st);
+
 // ---- muon.hip: the Muon optimizer (momentum -> Newton-Schulz -> update), bf16 work buffers, fp32 accumulation.
 // Batched products over stacked same-shape matrices (row strides ld*, batch strides s*, in elements); the final
 // scale is alpha * dalpha[batch * dalpha_stride] (dalpha: optional per-batch device scalars).

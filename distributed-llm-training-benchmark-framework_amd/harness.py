@@ -16,7 +16,8 @@ Extra flags (all optional): --accum-semantics, --grad-reduce, --dtype, --device,
 --profile, --debug-collectives, --fail-at-step, --timeout-min, --data-loader, --model-tier, --sliding-window,
 --doc-len, --context-parallel, --cp-layout, --activation-recompute, --head-chunk, --moe-experts, --moe-top-k,
 --moe-capacity-factor, --moe-aux-loss-coef, --moe-z-loss-coef, --moe-dropless, --qk-norm,
---attn-sinks, --attn-softcap, --final-softcap, --lm-z-loss-coef, --sandwich-norm, --ffn-act.
+--attn-sinks, --attn-softcap, --final-softcap, --lm-z-loss-coef, --sandwich-norm, --ffn-act,
+--fp8-linear.
 """
 import argparse
 import json
@@ -120,6 +121,11 @@ def build_parser():
     p.add_argument("--ffn-act", choices=["swiglu", "geglu"], default="swiglu",
                    help="causal tiers: the gated FFN's activation, silu(gate) * up or gelu_tanh(gate) * up (the Gemma "
                         "FFN), dense and mixture-of-experts; default: swiglu")
+    p.add_argument("--fp8-linear", action="store_true",
+                   help="causal tiers, bf16: the four dense products of every layer (qkv, o, gate|up, down) run on "
+                        "row-scaled FP8 (OCP E4M3 codes, one power-of-two scale per token / per weight channel) in "
+                        "the forward and the data gradient, on the FP8 matrix instruction; weight gradients, the LM "
+                        "head and the embedding stay 16-bit; not with --moe-experts or fp16 loss scaling; default: off")
     p.add_argument("--attn-softcap", type=float, default=0.0, metavar="C",
                    help="causal tiers: attention logit soft-capping, every score x becomes C * tanh(x / C) before the "
                         "softmax (Gemma-2 uses 50), in capped instantiations of the three attention kernels; not "
@@ -298,6 +304,19 @@ def check_ffn_act(act, mcfg, tier):
     mcfg.validate()
 
 
+def check_fp8_linear(on, mcfg, tier, loss_scaling=False):
+    """ValueError when ``--fp8-linear`` is set for a tier or a step it does not cover; sets it on ``mcfg``."""
+    if not on:
+        return
+    if not mcfg.causal:
+        raise ValueError(f"--fp8-linear needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} runs the reference's "
+                         "TinyGPT block, whose products stay 16-bit")
+    if loss_scaling:
+        raise ValueError("--fp8-linear is not supported with an fp16 step under dynamic loss scaling; use --dtype bf16")
+    mcfg.fp8_linear = True
+    mcfg.validate()
+
+
 def check_attn_sinks(on, mcfg, tier):
     """ValueError when ``--attn-sinks`` is set for a tier without causal attention; sets it on ``mcfg``."""
     if not on:
@@ -470,6 +489,7 @@ def train(args):
         check_attn_sinks(bool(getattr(args, "attn_sinks", False)), mcfg, args.tier)
         check_sandwich_norm(bool(getattr(args, "sandwich_norm", False)), mcfg, args.tier)
         check_ffn_act(getattr(args, "ffn_act", "swiglu"), mcfg, args.tier)
+        check_fp8_linear(bool(getattr(args, "fp8_linear", False)), mcfg, args.tier)
         check_attn_softcap(getattr(args, "attn_softcap", 0.0), bool(getattr(args, "attn_sinks", False)), mcfg,
                            args.tier)
         check_final_softcap(getattr(args, "final_softcap", 0.0), mcfg, args.tier)
@@ -508,6 +528,9 @@ def train(args):
         if (mcfg.sandwich_norm or mcfg.ffn_act != "swiglu") and is_main:
             print(f"decoder block: sandwich norms {'on' if mcfg.sandwich_norm else 'off'} (an RMSNorm on every "
                   f"sublayer's output before the residual add), gated FFN activation {mcfg.ffn_act}", flush=True)
+        if mcfg.fp8_linear and is_main:
+            print("FP8 linear layers: qkv, o, gate|up and down products on row-scaled E4M3 (forward and data gradient)",
+                  flush=True)
         if mcfg.attn_sinks and is_main:
             print(f"attention sinks: one learned logit per query head ({mcfg.n_head} per layer)", flush=True)
         if mcfg.attn_softcap and is_main:
@@ -683,6 +706,7 @@ def train(args):
             "head_chunk": head_chunk, "head_chunks": n_head_chunks,
             "attn_sinks": bool(mcfg.attn_sinks),
             "sandwich_norm": bool(mcfg.sandwich_norm), "ffn_act": str(mcfg.ffn_act),
+            "fp8_linear": bool(mcfg.fp8_linear),
             "attn_softcap": float(mcfg.attn_softcap),
             "final_softcap": float(mcfg.final_softcap),
             "lm_z_loss_coef": float(mcfg.lm_z_loss_coef),
@@ -790,6 +814,7 @@ def main(argv=None):
         check_attn_sinks(args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
         check_sandwich_norm(args.sandwich_norm, get_model_config(args.tier, args.seq_len), args.tier)
         check_ffn_act(args.ffn_act, get_model_config(args.tier, args.seq_len), args.tier)
+        check_fp8_linear(args.fp8_linear, get_model_config(args.tier, args.seq_len), args.tier)
         check_attn_softcap(args.attn_softcap, args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
         check_final_softcap(args.final_softcap, get_model_config(args.tier, args.seq_len), args.tier)
         check_lm_z_loss(args.lm_z_loss_coef, get_model_config(args.tier, args.seq_len), args.tier)

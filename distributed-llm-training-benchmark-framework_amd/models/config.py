@@ -83,6 +83,10 @@ class ModelConfig:
     # the gated FFN's activation (mistral arch): "swiglu" = silu(gate) * up, "geglu" = gelu_tanh(gate) * up (Gemma);
     # the GEGLU instantiations of the three gated-FFN kernels (csrc/elementwise.hip), dense and both MoE routings
     ffn_act: str = "swiglu"
+    # row-scaled FP8 linear layers (mistral arch, dense FFN): the four dense products of a layer (qkv, o, gate|up, down)
+    # run on OCP E4M3 codes with one power-of-two scale per row, forward and data gradient (csrc/gemm_fp8.hip; the
+    # contract is ops/ref.py fp8_quant_rows / gemm_fp8_nt).  Weight gradients, the LM head, the embedding stay 16-bit.
+    fp8_linear: bool = False
 
     def __post_init__(self):
         self.validate()
@@ -136,6 +140,14 @@ class ModelConfig:
         if self.ffn_act != "swiglu" and self.arch != "mistral":
             raise ValueError(f"ffn_act = {self.ffn_act!r} (the gated FFN's activation) needs the mistral arch, got arch "
                              f"{self.arch!r}")
+        if not isinstance(self.fp8_linear, bool):
+            raise ValueError(f"fp8_linear must be a bool, got {self.fp8_linear!r}")
+        if self.fp8_linear and self.arch != "mistral":
+            raise ValueError(f"--fp8-linear (fp8_linear, row-scaled FP8 linear layers) needs the mistral arch of the "
+                             f"causal tiers, got arch {self.arch!r}")
+        if self.fp8_linear and self.n_experts is not None:
+            raise ValueError("--fp8-linear (fp8_linear) is not supported together with --moe-experts: the experts' "
+                             "products and the grouped GEMMs are 16-bit only")
         k, cf = self.moe_top_k, self.moe_capacity_factor
         if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4):
             raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
@@ -222,7 +234,8 @@ class ModelConfig:
         adds no matrix product (its 2 * head_dim weights per layer are elementwise), like the other norms; nor does
         ``attn_sinks`` (one more softmax term per query row and head), ``attn_softcap`` (elementwise on the
         scores), ``final_softcap`` / ``lm_z_loss_coef`` (elementwise on the logits, inside the loss kernels),
-        ``sandwich_norm`` (two more row norms per layer) or ``ffn_act`` (elementwise)."""
+        ``sandwich_norm`` (two more row norms per layer), ``ffn_act`` (elementwise) or ``fp8_linear`` (the same products on
+        8-bit operands)."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d

@@ -194,6 +194,27 @@ def _ffn_out_fwd(cfg, x1, m, w_ffn_out, seed):
     return x2, rstd_m
 
 
+def _lin_fwd(model, unit, j, x2d, w):
+    """x W^T of dense product ``j`` of a layer (parameter ``w`` = ws[j]): the 16-bit path, or under ``cfg.fp8_linear``
+    the row-scaled FP8 path with the engine's cached codes of W (quantised per call where it caches none)."""
+    if not model.cfg.fp8_linear:
+        return F_.linear_fwd(x2d, w)
+    wq = model.rt.weight_q(unit, j, w)
+    return F_.linear_fp8_fwd(x2d, w, None if wq is None else wq[0])
+
+
+def _lin_dgrad(model, unit, j, dy2d, w):
+    """dY W of dense product ``j``: the 16-bit path with the engine's cached W^T, or under ``cfg.fp8_linear`` the FP8
+    path with the cached codes of W^T (else of the cached or a scratch 16-bit W^T, quantised per call)."""
+    rt = model.rt
+    if not model.cfg.fp8_linear:
+        return F_.linear_dgrad(dy2d, w, rt.weight_t(unit, j, w))
+    wq = rt.weight_q(unit, j, w) if dy2d.shape[0] % 128 == 0 else None
+    if wq is not None:
+        return F_.linear_fp8_dgrad(dy2d, w, wq[1])
+    return F_.linear_fp8_dgrad(dy2d, w, None, rt.weight_t(unit, j, w))
+
+
 def _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn):
     """RoPE in place on the q|k columns of ``qkv`` (rows of T positions); with ``qkn`` = (wq, wk) the fused
     QK-norm + RoPE pass instead.  Returns ``raw`` (None without QK-norm)."""
@@ -320,7 +341,7 @@ class _LayerFn(torch.autograd.Function):
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
         _, h1, _, rstd1 = F_.norm_fwd(x, None, w_in, None, cfg.norm_eps, True)
-        qkv = F_.linear_fwd(h1, wqkv)
+        qkv = _lin_fwd(model, unit, 1, h1, wqkv)
         qd, kd = Hq * D, Hkv * D
         # document mask: the forward's bounds (window folded in) replace the window, and stay for the backward
         bounds = model._cur_bounds
@@ -332,7 +353,7 @@ class _LayerFn(torch.autograd.Function):
             o, lse, aux = F_.attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
                                       1.0 / math.sqrt(D), True, 0.0, rt.seed, 0, window=window, bounds=bounds,
                                       sink=sink, softcap=cfg.attn_softcap)
-        a = F_.linear_fwd(o, wo)
+        a = _lin_fwd(model, unit, 2, o, wo)
         jo = _out_norm_index(cfg, ws)            # sandwich norms: ws[jo] the attention site's, ws[jo + 1] the FFN's
         if jo is None:
             x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
@@ -348,9 +369,9 @@ class _LayerFn(torch.autograd.Function):
                 router_losses = rest[0]
         else:
             wgu, wd = ws[4:6]
-            gu = F_.linear_fwd(h2, wgu)
+            gu = _lin_fwd(model, unit, 4, h2, wgu)
             hh = F_.swiglu_fwd(gu, cfg.ffn_act)
-            m = F_.linear_fwd(hh, wd)
+            m = _lin_fwd(model, unit, 5, hh, wd)
         x2, rstd_m = _ffn_out_fwd(cfg, x1, m, None if jo is None else ws[jo + 1], rt.seed)
         rt.release_forward(unit)
         ctx.model, ctx.i = model, i
@@ -398,17 +419,17 @@ class _LayerFn(torch.autograd.Function):
         else:
             wgu, wd = ws[4:6]
             F_.linear_wgrad(dm, hh, s[5][0], None, s[5][1])
-            dhh = F_.linear_dgrad(dm, wd, rt.weight_t(unit, 5, wd))
+            dhh = _lin_dgrad(model, unit, 5, dm, wd)
             dgu = F_.swiglu_bwd(dhh, gu, cfg.ffn_act)
             F_.linear_wgrad(dgu, h2, s[4][0], None, s[4][1])
-            dh2 = F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, 4, wgu))
+            dh2 = _lin_dgrad(model, unit, 4, dgu, wgu)
         if jo is None:
             dx1 = F_.norm_bwd(dh2, x1, w_post, None, rstd2, dx2, s[3][0], None, s[3][1], True, red=red)
             da = dx1
         else:                   # dx1 = dx2 + the pre-norm's backward, da = the attention site's out-norm backward of dx1
             dx1, da = F_.sandwich_bwd(dh2, x1, w_post, rstd2, dx2, a, ws[jo], rstd_a, s[3], s[jo], red)
         F_.linear_wgrad(da, o, s[2][0], None, s[2][1])
-        do = F_.linear_dgrad(da, wo, rt.weight_t(unit, 2, wo))
+        do = _lin_dgrad(model, unit, 2, da, wo)
         qd, kd = Hq * D, Hkv * D
         dqkv = torch.empty_like(qkv)
         window = 0 if ctx.bounds is not None else cfg.sliding_window or 0
@@ -425,7 +446,7 @@ class _LayerFn(torch.autograd.Function):
             _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, s[nb] if qkn else None, s[nb + 1] if qkn else None, red)
         ctx.bounds = None
         F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
-        dh1 = F_.linear_dgrad(dqkv, wqkv, rt.weight_t(unit, 1, wqkv))
+        dh1 = _lin_dgrad(model, unit, 1, dqkv, wqkv)
         dx = F_.norm_bwd(dh1, x, w_in, None, rstd1, dx1, s[0][0], None, s[0][1], True, red=red)
         if shared is None:
             red.flush()
@@ -621,27 +642,27 @@ def _layer_backward_recompute(ctx, dx2):
         ctx.sand = None
     # ---- MLP half
     if full:
-        a = F_.linear_fwd(o, wo)
+        a = _lin_fwd(model, unit, 2, o, wo)
         if jo is None:
             x1, h2, _, rstd2 = F_.norm_fwd(x, a, w_post, None, cfg.norm_eps, True)
             a = None
         else:
             x1, h2, rstd_a, rstd2 = F_.sandwich_fwd(x, a, ws[jo], w_post, cfg.norm_eps)
-        gu = F_.linear_fwd(h2, wgu)
+        gu = _lin_fwd(model, unit, 4, h2, wgu)
     else:
         h2 = F_.norm_apply(x1, w_post, None, None, rstd2, True)
     dm = dx2
     if jo is not None:
         dm = F_.norm_bwd(dx2, m, ws[jo + 1], None, rstd_m, None, s[jo + 1][0], None, s[jo + 1][1], True, red=red)
         del m, rstd_m
-    dhh = F_.linear_dgrad(dm, wd, rt.weight_t(unit, 5, wd))
+    dhh = _lin_dgrad(model, unit, 5, dm, wd)
     dgu, hh = F_.swiglu_bwd_h(dhh, gu, cfg.ffn_act)
     del dhh, gu
     F_.linear_wgrad(dm, hh, s[5][0], None, s[5][1])
     del hh, dm
     F_.linear_wgrad(dgu, h2, s[4][0], None, s[4][1])
     del h2
-    dh2 = F_.linear_dgrad(dgu, wgu, rt.weight_t(unit, 4, wgu))
+    dh2 = _lin_dgrad(model, unit, 4, dgu, wgu)
     del dgu
     if jo is None:
         dx1 = F_.norm_bwd(dh2, x1, w_post, None, rstd2, dx2, s[3][0], None, s[3][1], True, red=red)
@@ -650,13 +671,13 @@ def _layer_backward_recompute(ctx, dx2):
         dx1, da = F_.sandwich_bwd(dh2, x1, w_post, rstd2, dx2, a, ws[jo], rstd_a, s[3], s[jo], red)
     del dh2, x1, rstd2, dx2, a, rstd_a
     F_.linear_wgrad(da, o, s[2][0], None, s[2][1])
-    do = F_.linear_dgrad(da, wo, rt.weight_t(unit, 2, wo))
+    do = _lin_dgrad(model, unit, 2, da, wo)
     del da
     # ---- attention half
     window = 0 if ctx.bounds is not None else cfg.sliding_window or 0
     if full:
         _, h1, _, rstd1 = F_.norm_fwd(x, None, w_in, None, cfg.norm_eps, True)
-        qkv = F_.linear_fwd(h1, wqkv)
+        qkv = _lin_fwd(model, unit, 1, h1, wqkv)
         if model.cp is not None:      # the re-gather: one more all-gather per layer, in layer order on every rank
             aux, raw = _cp_rope_gather(model, qkv, Hq, Hkv, D, qkn)
         else:
@@ -679,7 +700,7 @@ def _layer_backward_recompute(ctx, dx2):
     del qkv, aux, o, do, lse, raw
     F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
     del h1
-    dh1 = F_.linear_dgrad(dqkv, wqkv, rt.weight_t(unit, 1, wqkv))
+    dh1 = _lin_dgrad(model, unit, 1, dqkv, wqkv)
     del dqkv
     dx = F_.norm_bwd(dh1, x, w_in, None, rstd1, dx1, s[0][0], None, s[0][1], True, red=red)
     if shared is None:

@@ -931,6 +931,69 @@ def linear_dgrad(dy2d, w, wt=None):
     return y if y is not None else torch.mm(dy2d, rhs)
 
 
+# Row-scaled FP8 linear layers (csrc/gemm_fp8.hip; the contract is ref.py's): E4M3 codes with one power-of-two scale
+# per row, per token for the activations, per output channel (forward) / input channel (data gradient) for W.
+fp8_gemm_calls = 0          # products issued through gemm_fp8_nt on the GPU (tests check that the path ran)
+
+
+def fp8_quant_rows(x, q_out=None, s_out=None):
+    """(codes uint8, scales f32) of the rows of x [R, K], or of a batch [nb, R, K] of equally spaced matrices in one
+    launch (GPU)."""
+    if _gpu(x):
+        q, s = ext().fp8_quant_rows(x, q_out, s_out)
+        return q, s
+    q, s = ref.fp8_quant_rows(x)
+    return _into(q_out, q), _into(s_out, s)
+
+
+def gemm_fp8_nt(qa, sa, qb, sb, dtype=torch.bfloat16, cfg=-1):
+    """c [M, N] = round16(sa[m] sb[n] sum_k dec(qa[m, k]) dec(qb[n, k])) in ``dtype`` (bf16 or fp16).  M, N, K
+    multiples of 128 (``ref.fp8_supported``); there is no other GPU path: a refused shape is an error."""
+    global fp8_gemm_calls
+    if _gpu(qa):
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"gemm_fp8_nt writes bf16 or fp16 on the GPU, not {dtype}")
+        fp8_gemm_calls += 1
+        return ext().gemm_fp8_nt(qa, sa, qb, sb, dtype == torch.float16, None, cfg)
+    return ref.gemm_fp8_nt(qa, sa, qb, sb, dtype)
+
+
+def _fp8_ok(a, b_rows, b_cols, *ts):
+    """The FP8 path takes a [M, K] against a [b_rows, b_cols = K] weight: tile-aligned shapes and, on the GPU, 16-bit
+    row-major operands with 16-byte aligned rows (the quantiser's loads)."""
+    if a.dim() != 2 or a.shape[1] != b_cols or not ref.fp8_supported(a.shape[0], b_rows, b_cols):
+        return False
+    if not _gpu(a):
+        return True
+    return all(t.is_cuda and t.dim() == 2 and t.dtype == a.dtype and t.dtype in (torch.bfloat16, torch.float16)
+               and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0 for t in (a,) + ts)
+
+
+def linear_fp8_fwd(x2d, w, wq=None):
+    """x W^T on the FP8 path; ``wq`` = (codes, scales) of W's rows if cached (parallel/engine.py ``weight_q``), else
+    W is quantised here.  A shape or layout the path does not take runs :func:`linear_fwd`."""
+    if not _fp8_ok(x2d, w.shape[0], w.shape[1], *(() if wq is not None else (w,))):
+        return linear_fwd(x2d, w)
+    qa, sa = fp8_quant_rows(x2d)
+    qb, sb = wq if wq is not None else fp8_quant_rows(w)
+    return gemm_fp8_nt(qa, sa, qb, sb, x2d.dtype)
+
+
+def linear_fp8_dgrad(dy2d, w, wtq=None, wt=None):
+    """dY W on the FP8 path; ``wtq`` = (codes, scales) of W^T's rows if cached, else the 16-bit W^T (``wt`` if
+    given, or a scratch transpose) is quantised here.  A shape or layout the path does not take runs
+    :func:`linear_dgrad`."""
+    if not _fp8_ok(dy2d, w.shape[1], w.shape[0], *(() if wtq is not None else (w,) if wt is None else (wt,))):
+        return linear_dgrad(dy2d, w, wt)
+    qa, sa = fp8_quant_rows(dy2d)
+    if wtq is None:
+        if wt is None:
+            wt = torch.empty(w.shape[1], w.shape[0], dtype=w.dtype, device=w.device)
+            transpose_into(w if w.is_contiguous() else w.contiguous(), wt)
+        wtq = fp8_quant_rows(wt)
+    return gemm_fp8_nt(qa, sa, wtq[0], wtq[1], dy2d.dtype)
+
+
 # hipBLASLt runs a product fastest with both operands K-contiguous (1.48-1.52 PFLOP/s on
 # Mistral-7B's [4096 x 4096-28672] shapes); a weight gradient dY^T X has neither (dY^T is an
 # M-contiguous view, X N-contiguous: 1.03-1.04 PFLOP/s), and one K-contiguous side already gives

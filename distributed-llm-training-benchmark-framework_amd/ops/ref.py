@@ -201,6 +201,58 @@ def swiglu_bwd_h(dh, gu, act="silu"):
     return swiglu_bwd(dh, gu, act), swiglu_fwd(gu, act)
 
 
+# ---- row-scaled FP8 linear layers (csrc/gemm_fp8.hip): OCP E4M3 codes with one power-of-two scale per row, per token
+# for activations and per output channel (forward) / input channel (data gradient) for weights
+def fp8_supported(M, N, K):
+    """The shapes the FP8 product takes (the kernel's tiles): positive multiples of 128; others run 16-bit."""
+    return min(M, N, K) > 0 and M % 128 == 0 and N % 128 == 0 and K % 128 == 0
+
+
+def fp8_quant_rows(x):
+    """(q uint8 [R, K], s f32 [R]) of x [R, K]: s = 2^e with e = ceil(log2(amax / 448)) clamped to [-126, 127], the
+    smallest power of two that brings the row's amax = max |x| to 448 or below (1 for an all-zero row), and q =
+    E4M3(x / s), round to nearest even; the division is exact.  A row whose amax is inf or NaN has s = NaN and codes 0.
+    The exponent is read from amax's bits (448 = 1.75 * 2^8: a mantissa above 1.75 needs one more), as adamw.hip's
+    block scales are."""
+    xf = x if x.dtype == torch.float64 else x.float()         # float64 rows: a float64 evaluation of the same rule
+    amax = xf.abs().amax(dim=1).float().contiguous()
+    bits = amax.view(torch.int32).to(torch.int64) & 0x7FFFFFFF
+    bad = bits >= 0x7F800000
+    e = (((bits + 0x1FFFFF) >> 23) - 135).clamp(-126, 127)
+    e = torch.where(bits == 0, torch.zeros_like(e), e)
+    s = ((e + 127) << 23).to(torch.int32).view(torch.float32)
+    q = (xf / s[:, None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    q = torch.where(bad[:, None], torch.zeros_like(q), q)
+    return q, torch.where(bad, torch.full_like(s, float("nan")), s)
+
+
+def fp8_dec(q):
+    """The fp32 values of E4M3 codes."""
+    return q.view(torch.float8_e4m3fn).float()
+
+
+def gemm_fp8_nt(qa, sa, qb, sb, dtype=torch.bfloat16):
+    """c [M, N] = round((sum_k dec(qa[m, k]) dec(qb[n, k])) * sa[m] * sb[n]) to ``dtype``: exact products, fp32
+    accumulation (float64 for a float64 ``dtype``), the row scale applied before the column scale, one rounding."""
+    wide = torch.float64 if dtype == torch.float64 else torch.float32
+    acc = fp8_dec(qa).to(wide) @ fp8_dec(qb).to(wide).t()
+    return ((acc * sa[:, None]) * sb[None, :]).to(dtype)
+
+
+def linear_fp8_fwd(x2d, w, wq=None):
+    """x W^T with x quantised per token and W per output channel; ``wq``: W's (codes, scales) if already made."""
+    qa, sa = fp8_quant_rows(x2d)
+    qb, sb = wq if wq is not None else fp8_quant_rows(w)
+    return gemm_fp8_nt(qa, sa, qb, sb, x2d.dtype)
+
+
+def linear_fp8_dgrad(dy2d, w, wtq=None):
+    """dY W with dY quantised per token and W per input channel (the rows of W^T); ``wtq``: W^T's (codes, scales)."""
+    qa, sa = fp8_quant_rows(dy2d)
+    qb, sb = wtq if wtq is not None else fp8_quant_rows(w.t().contiguous())
+    return gemm_fp8_nt(qa, sa, qb, sb, dy2d.dtype)
+
+
 def rope_tables(T, D, theta, device=None):
     half = D // 2
     inv = 1.0 / (theta ** (torch.arange(0, half, dtype=torch.float64) * 2.0 / D))

@@ -92,7 +92,14 @@ class Engine(ParamRuntime):
         self._cache_wt = False   # subclasses: True where parameters stay resident between steps
         self._wt = {}            # (unit index, param index) -> (W view, W^T view of a stacked buffer)
         self._wt_stack = {}      # (param index, shape) -> [units, K, N] buffer of transposes
-        self._wt_epoch = -1      # optimizer step the cached transposes belong to
+        self._wt_epoch = -1      # optimizer step the cached transposes (and FP8 codes) belong to
+        self._cache_wq = False   # subclasses: True where parameters stay resident between steps (weight_q)
+        self._wqc = {}            # (unit index, param index) -> (W view, stack row, kind)
+        self._wq_stack = {}      # kind (param index, shape) -> (Wq, sW, WTq, sWT) stacked over the units
+        self._wq_scratch = {}    # kind -> a 16-bit [K, N] buffer for W^T where no transpose is cached
+        if getattr(getattr(model, "cfg", None), "fp8_linear", False) and self.scaler is not None:
+            raise ValueError("--fp8-linear is not supported with an fp16 step under dynamic loss scaling: scaled "
+                             "gradients would set the E4M3 row scales; use --dtype bf16")
         if cfg.optimizer not in ("adamw", "muon"):
             raise ValueError(f"optimizer must be adamw or muon, not {cfg.optimizer!r}")
         if cfg.optimizer == "muon":
@@ -244,9 +251,7 @@ class Engine(ParamRuntime):
         instead of one launch per block."""
         if not self._cache_wt or w.dim() != 2 or not w.is_cuda:
             return None
-        if self._wt_epoch != self.opt_steps:
-            self._refresh_weight_t()
-            self._wt_epoch = self.opt_steps
+        self._refresh_weight_caches()
         key = (unit.index, i)
         hit = self._wt.get(key)
         if hit is not None:
@@ -266,6 +271,85 @@ class Engine(ParamRuntime):
         ext().transpose_into(w, wt)          # first use: transpose now
         self._wt[key] = (w, wt)
         return wt
+
+    def _refresh_weight_caches(self):
+        """Once per optimizer step, at the first use after it: the cached transposes, then the FP8 codes."""
+        if self._wt_epoch != self.opt_steps:
+            self._refresh_weight_t()
+            self._refresh_weight_q()
+            self._wt_epoch = self.opt_steps
+
+    # ------------------------------------------------------------------ cached FP8 weight codes
+    def weight_q(self, unit, i, w):
+        """Cached ((Wq, sW), (WTq, sWT)) for the FP8 linears (``cfg.fp8_linear``; engines whose parameters stay
+        resident between optimizer steps, at any size: the codes of W and of W^T cost 2 bytes per weight element).
+        Like :meth:`weight_t` the codes and scales of one parameter kind live in stacked buffers, one row per unit in
+        the order of the flat buffers, filled at first use and refreshed once per optimizer step -- under the same
+        epoch as the transposes -- by one batched quantiser launch per kind for W.  W^T's codes come from the cached
+        16-bit W^T where :meth:`weight_t` holds one (batched too), else from a scratch transpose per matrix."""
+        if (not self._cache_wq or w.dim() != 2 or not w.is_cuda or w.shape[0] % 128 or w.shape[1] % 128
+                or not w.is_contiguous() or w.data_ptr() % 16):
+            return None
+        self._refresh_weight_caches()
+        key = (unit.index, i)
+        ent = self._wqc.get(key)
+        if ent is None:
+            g = (i, tuple(w.shape))
+            units = self.model.units()
+            order = reversed(units) if getattr(self, "wgrad_rows_reversed", True) else units
+            rows = [u.index for u in order if len(u.shapes) > i and u.shapes[i] == g[1]]
+            stack = self._wq_stack.get(g)
+            if stack is None:
+                n, (N, K) = len(rows), w.shape
+                u8 = dict(dtype=torch.uint8, device=w.device)
+                f32 = dict(dtype=torch.float32, device=w.device)
+                stack = self._wq_stack[g] = (torch.empty((n, N, K), **u8), torch.empty((n, N), **f32),
+                                             torch.empty((n, K, N), **u8), torch.empty((n, K), **f32))
+            r = rows.index(unit.index)
+            ent = self._wqc[key] = (w, r, g)
+            self._quant_weights(g, [(key, ent)])      # first use: quantise now
+        q, s, qt, st = self._wq_stack[ent[2]]
+        return (q[ent[1]], s[ent[1]]), (qt[ent[1]], st[ent[1]])
+
+    def _refresh_weight_q(self):
+        groups = {}
+        for key, ent in self._wqc.items():
+            groups.setdefault(ent[2], []).append((key, ent))
+        for g, items in groups.items():
+            self._quant_weights(g, sorted(items, key=lambda it: it[1][1]))
+
+    def _quant_weights(self, g, items):
+        """Quantise W and W^T of ``items`` (cache entries of kind ``g``, in stack-row order) into their stack rows."""
+        from .wgrad import strided_batch
+        C = ext()
+        q, s, qt, st = self._wq_stack[g]
+        r0, n = items[0][1][1], len(items)
+        run = [e[1] for _, e in items] == list(range(r0, r0 + n))       # consecutive stack rows
+
+        def batch(ts):
+            b = strided_batch(ts) if run and n > 1 else None
+            return b if b is not None and b.stride(0) % 8 == 0 else None
+
+        W = batch([e[0] for _, e in items])
+        if W is not None:
+            C.fp8_quant_rows(W, q[r0:r0 + n], s[r0:r0 + n])
+        wts = [self._wt.get(key) for key, _ in items]
+        WT = batch([t[1] for t in wts]) if all(t is not None for t in wts) else None
+        if WT is not None:
+            C.fp8_quant_rows(WT, qt[r0:r0 + n], st[r0:r0 + n])
+        for (key, (w, r, _)), t in zip(items, wts):
+            if W is None:
+                C.fp8_quant_rows(w, q[r], s[r])
+            if WT is None:
+                wt = t[1] if t is not None else self._wq_scratch.get(g)
+                if wt is None:
+                    wt = self._wq_scratch[g] = torch.empty((w.shape[1], w.shape[0]), dtype=w.dtype, device=w.device)
+                if t is None:
+                    C.transpose_into(w, wt)
+                C.fp8_quant_rows(wt, qt[r], st[r])
+
+    def weight_q_cache_bytes(self) -> int:
+        return sum(t.numel() * t.element_size() for st in self._wq_stack.values() for t in st)
 
     def _refresh_weight_t(self):
         from .wgrad import strided_batch

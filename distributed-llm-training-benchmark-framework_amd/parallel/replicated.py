@@ -201,6 +201,7 @@ class ReplicatedEngine(Engine):
         self._defer_opt = (self.stage >= 1 and self.world > 1 and self._overlap and
                            bool(cfg.extra.get("defer_opt", os.environ.get("DLTB_DEFER_OPT", "1") == "1")))
         self._cache_wt = True    # cached W^T of every matrix for the NT-form dgrad GEMMs (engine.py)
+        self._cache_wq = True    # ... and, under fp8_linear, the FP8 codes of W and W^T (engine.py weight_q)
         self._pending = [len(b.units) for b in L.buckets]
         self._bucket_of = L.unit_bucket
         self._wq = WgradQueue()
@@ -650,6 +651,7 @@ class ReplicatedEngine(Engine):
         e = self.flat_param.element_size()
         return {"param_bytes": self.flat_param.numel() * e, "grad_bytes": self.flat_grad.numel() * e,
                 "optimizer_bytes": self.opt.state_bytes, "optimizer_state": self.opt.state,
+                "weight_q_cache_bytes": self.weight_q_cache_bytes(),
                 "buckets": len(self.layout.buckets),
                 "bucket_mb": [round(b.numel * e / 2**20, 2) for b in self.layout.buckets]}
 

@@ -71,6 +71,12 @@ class ParamRuntime:
         M = 2048 -- for the price of one transpose per optimizer step."""
         return None
 
+    def weight_q(self, unit: Unit, i: int, w: torch.Tensor):
+        """((Wq, sW), (WTq, sWT)): the row-scaled FP8 codes and scales of 2-D parameter ``i`` of ``unit`` and of its
+        transpose (ops/ref.py ``fp8_quant_rows``), or None.  Engines whose parameters stay resident between optimizer
+        steps cache them per step (parallel/engine.py); elsewhere the FP8 linears quantise W per call."""
+        return None
+
     # backward
     def acquire_backward(self, unit: Unit) -> List[torch.Tensor]:
         return [p.detach() for p in unit.params]

@@ -261,6 +261,9 @@ class ShardedEngine(Engine):
         nparam = sum(u.numel for u in self.model.units())
         self._cache_wt = (self.world == 1 and self.accum > 1 and nparam < 2_000_000_000
                           and bool(cfg.extra.get("cache_weight_t", True)))
+        # the FP8 codes of W and W^T (engine.py weight_q) replace operands instead of adding a pass, so they are cached
+        # wherever the gathered view is the resident shard, at any model size and window length
+        self._cache_wq = self.world == 1
         # world > 1: the gathered W is a transient buffer, so the cache keeps its own transposed copy,
         # made the first time a unit's backward needs it in an accumulation window (the parameters
         # do not change inside a window) and reused by the window's other micro-steps -- one LDS
@@ -701,6 +704,7 @@ class ShardedEngine(Engine):
                 "held_grad_bytes": sum(t.numel() * t.element_size() for t in self._held_grads
                                        if not any(t is g.grad_buf for g in self.groups)),
                 "weight_t_cache_bytes": sum(t.numel() * t.element_size() for t, _ in (self._wt_multi or {}).values()),
+                "weight_q_cache_bytes": self.weight_q_cache_bytes(),
                 "gather_pool_bytes": sum(b.numel() * e for bufs in self._gpool.values() for b in bufs)}
 
     def full_state_dict(self):
