@@ -194,6 +194,21 @@ void dltb_attn_doc_bounds(const int64_t* idx, int* bounds, int B, int T, int64_t
                           hipStream_t st);
 void dltb_attn_init_attributes();
 
+// ---- linear_attn.hip: chunked fixed-decay linear attention, o[i] = r[g,i] scale sum_{j<=i} gamma_g^(i-j) (q[i].k[j]) v[j]
+// with r[g,i] = sqrt((1 - gamma_g) / (1 - gamma_g^(i+1))) and g = h / (Hq / Hkv).  q / k / v / o / dout / dq / dk / dv:
+// token-major strided rows as for dltb_attn_fwd (16-byte aligned, strides multiples of 8); l2g: fp32 [Hkv] log2(gamma),
+// strictly negative (not checked: it is device memory).
+// D in {64, 128}, T a multiple of dltb_linear_attn_chunk().  local (fp32) and state (16-bit): workspaces of
+// B Hkv (T / chunk) D D elements each; nothing in them outlives the call (the backward rebuilds the states).
+int dltb_linear_attn_chunk();
+bool dltb_linear_attn_supported(int D, int T);
+void dltb_linear_attn_fwd(const void* q, const void* k, const void* v, void* o, const float* l2g, float* local,
+                          void* state, long qs, long ks, long vs, long os, int B, int T, int Hq, int Hkv, int D,
+                          float scale, hipStream_t st);
+void dltb_linear_attn_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
+                          const float* l2g, float* local, void* state, long qs, long ks, long vs, long dos, long dqs,
+                          long dks, long dvs, int B, int T, int Hq, int Hkv, int D, float scale, hipStream_t st);
+
 // ---- batched column reductions (colreduce.hip)
 #ifndef DLTB_LAUNCHER_TYPES   // types once (launchers_f16.h repeats only the declarations)
 #define DLTB_LAUNCHER_TYPES

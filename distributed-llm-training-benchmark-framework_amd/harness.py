@@ -126,6 +126,11 @@ def build_parser():
                         "row-scaled FP8 (OCP E4M3 codes, one power-of-two scale per token / per weight channel) in "
                         "the forward and the data gradient, on the FP8 matrix instruction; weight gradients, the LM "
                         "head and the embedding stay 16-bit; not with --moe-experts or fp16 loss scaling; default: off")
+    p.add_argument("--linear-attn", action="store_true",
+                   help="causal tiers: every layer mixes tokens with fixed-decay linear attention (the RetNet / "
+                        "lightning form, one decay 1 - 2^(-5 - 8 g / kv_heads) per KV head, a [head_dim, head_dim] "
+                        "state, linear in the sequence length) in softmax attention's place; no parameter; not with "
+                        "--context-parallel, --sliding-window, --doc-len, --attn-sinks or --attn-softcap; default: off")
     p.add_argument("--attn-softcap", type=float, default=0.0, metavar="C",
                    help="causal tiers: attention logit soft-capping, every score x becomes C * tanh(x / C) before the "
                         "softmax (Gemma-2 uses 50), in capped instantiations of the three attention kernels; not "
@@ -317,6 +322,21 @@ def check_fp8_linear(on, mcfg, tier, loss_scaling=False):
     mcfg.validate()
 
 
+def check_linear_attn(on, mcfg, tier, cp=1):
+    """ValueError when ``--linear-attn`` is set for a tier or a job it does not cover (``mcfg`` carries the job's other
+    attention switches by now); sets it on ``mcfg``."""
+    if not on:
+        return
+    if not mcfg.causal:
+        raise ValueError(f"--linear-attn needs a causal tier (M7B, M7B_narrow, mtiny); tier {tier} has the reference's "
+                         "non-causal softmax attention")
+    if cp > 1:
+        raise ValueError("--linear-attn is not supported together with --context-parallel: the chunk state is not "
+                         "passed between ranks")
+    mcfg.linear_attn = True
+    mcfg.validate()
+
+
 def check_attn_sinks(on, mcfg, tier):
     """ValueError when ``--attn-sinks`` is set for a tier without causal attention; sets it on ``mcfg``."""
     if not on:
@@ -494,6 +514,7 @@ def train(args):
                            args.tier)
         check_final_softcap(getattr(args, "final_softcap", 0.0), mcfg, args.tier)
         check_lm_z_loss(getattr(args, "lm_z_loss_coef", 0.0), mcfg, args.tier)
+        check_linear_attn(bool(getattr(args, "linear_attn", False)), mcfg, args.tier, cp_n)
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -707,6 +728,7 @@ def train(args):
             "attn_sinks": bool(mcfg.attn_sinks),
             "sandwich_norm": bool(mcfg.sandwich_norm), "ffn_act": str(mcfg.ffn_act),
             "fp8_linear": bool(mcfg.fp8_linear),
+            "linear_attn": bool(mcfg.linear_attn),
             "attn_softcap": float(mcfg.attn_softcap),
             "final_softcap": float(mcfg.final_softcap),
             "lm_z_loss_coef": float(mcfg.lm_z_loss_coef),
@@ -818,6 +840,12 @@ def main(argv=None):
         check_attn_softcap(args.attn_softcap, args.attn_sinks, get_model_config(args.tier, args.seq_len), args.tier)
         check_final_softcap(args.final_softcap, get_model_config(args.tier, args.seq_len), args.tier)
         check_lm_z_loss(args.lm_z_loss_coef, get_model_config(args.tier, args.seq_len), args.tier)
+        cfg0 = get_model_config(args.tier, args.seq_len)      # with the job's other attention switches, as train() has it
+        if cfg0.causal:
+            cfg0.sliding_window = args.sliding_window
+            cfg0.doc_eos_id = None if args.doc_len is None else cfg0.vocab_size - 1
+            cfg0.attn_sinks, cfg0.attn_softcap = bool(args.attn_sinks), float(args.attn_softcap)
+        check_linear_attn(args.linear_attn, cfg0, args.tier, args.context_parallel)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

@@ -87,6 +87,12 @@ class ModelConfig:
     # run on OCP E4M3 codes with one power-of-two scale per row, forward and data gradient (csrc/gemm_fp8.hip; the
     # contract is ops/ref.py fp8_quant_rows / gemm_fp8_nt).  Weight gradients, the LM head, the embedding stay 16-bit.
     fp8_linear: bool = False
+    # fixed-decay linear attention (mistral arch) in softmax attention's place in every layer, the RetNet / lightning
+    # form: o[i] = r[g,i] / sqrt(head_dim) * sum_{j <= i} gamma_g^(i-j) (q[i] . k[j]) v[j] with one decay per KV head,
+    # gamma_g = 1 - 2^(-5 - 8 g / kv_heads), and r[g,i] = sqrt((1 - gamma_g) / (1 - gamma_g^(i+1))); linear in T through
+    # a [head_dim, head_dim] state per KV head (csrc/linear_attn.hip).  No parameter, no lse.  Causal only; not with
+    # sliding_window, doc_eos_id, attn_sinks, attn_softcap or dropout.
+    linear_attn: bool = False
 
     def __post_init__(self):
         self.validate()
@@ -148,6 +154,21 @@ class ModelConfig:
         if self.fp8_linear and self.n_experts is not None:
             raise ValueError("--fp8-linear (fp8_linear) is not supported together with --moe-experts: the experts' "
                              "products and the grouped GEMMs are 16-bit only")
+        if not isinstance(self.linear_attn, bool):
+            raise ValueError(f"linear_attn must be a bool, got {self.linear_attn!r}")
+        if self.linear_attn:
+            for bad, why in ((self.arch != "mistral", f"needs the mistral arch of the causal tiers, got arch {self.arch!r}"),
+                             (not self.causal, "needs causal=True"),
+                             (self.dropout > 0, f"has no dropout, got dropout {self.dropout!r}"),
+                             (self.sliding_window is not None, "is not supported together with sliding_window"),
+                             (self.doc_eos_id is not None, "is not supported together with doc_eos_id (the state is "
+                                                           "not reset at document boundaries)"),
+                             (self.attn_sinks, "is not supported together with attn_sinks (there is no softmax)"),
+                             (self.attn_softcap > 0, "is not supported together with attn_softcap (there is no "
+                                                     "softmax)"),
+                             (self.head_dim not in (64, 128), f"needs head_dim 64 or 128, got {self.head_dim}")):
+                if bad:
+                    raise ValueError(f"--linear-attn (linear_attn, fixed-decay linear attention) {why}")
         k, cf = self.moe_top_k, self.moe_capacity_factor
         if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4):
             raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
@@ -235,7 +256,12 @@ class ModelConfig:
         ``attn_sinks`` (one more softmax term per query row and head), ``attn_softcap`` (elementwise on the
         scores), ``final_softcap`` / ``lm_z_loss_coef`` (elementwise on the logits, inside the loss kernels),
         ``sandwich_norm`` (two more row norms per layer), ``ffn_act`` (elementwise) or ``fp8_linear`` (the same products on
-        8-bit operands)."""
+        8-bit operands).  With ``linear_attn`` the attention term is the state form, independent of T: per token and
+        layer the forward multiplies the chunk's causal half of the scores and of their product with V
+        (2 * C/2 * head_dim each per query head, C = ``ops.ref.LINEAR_ATTN_CHUNK``), the query by the state (2 * head_dim^2 per query head) and
+        builds the state (2 * head_dim^2 per KV head); times 3 for forward + backward,
+        ``attn = 6 * L * (d * (C + head_dim) + kv_dim * head_dim)``.  The states the backward rebuilds are not
+        counted, and no T x T product is."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d
@@ -251,6 +277,9 @@ class ModelConfig:
             attn = 12 * L * d * (w * (seq_len - w) + w * w / 2.0) / seq_len
         if visible_pairs_per_row is not None:
             attn = 12 * L * d * float(visible_pairs_per_row) / seq_len
+        if self.linear_attn:
+            from ..ops.ref import LINEAR_ATTN_CHUNK as C      # the kernels' chunk (csrc/linear_attn.hip kC)
+            attn = 6.0 * L * (d * (C + self.head_dim) + self.kv_heads * self.head_dim * self.head_dim)
         return 6.0 * n_mat + attn
 
 

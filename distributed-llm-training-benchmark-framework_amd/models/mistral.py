@@ -46,6 +46,11 @@ With ``cfg.final_softcap`` = C > 0 the head's loss is formed from ``c = C * tanh
 c exists in fp32 registers only; the row mean, the 1 / count scale and what the backward keeps are unchanged (the
 kept lse is that of c).  The logits handed back to a caller are the capped ones, rounded to the model's format.
 
+With ``cfg.linear_attn`` every layer calls ``linear_attn_fwd`` / ``linear_attn_bwd`` (csrc/linear_attn.hip) where it
+would call ``attn_fwd`` / ``attn_bwd``: fixed-decay linear attention on the same q, k, v (after RoPE, or the fused
+QK-norm + RoPE), one decay per KV head.  There is no lse and the backward rebuilds the chunk states, so both recompute
+modes keep ``o`` for the mixer and never re-run it.  ``ContextParallel.attach`` refuses such a model.
+
 With ``cfg.sandwich_norm`` every sublayer's output goes through its own RMSNorm before it joins the residual stream,
 ``x1 = x + RMSNorm(a; self_attn.out_norm)`` and ``x2 = x1 + RMSNorm(m; mlp.out_norm)`` (m: the dense FFN's output or the
 MoE combine), on top of the two pre-norms.  The two [n_embd] weights sit in the layer's parameter list after the
@@ -326,6 +331,15 @@ def _cp_attn_bwd(model, qkv, kv, o, do, lses, dqkv, Hq, Hkv, D, window, bounds, 
         F_.reduce_partials(red, part[1], sk[0], sk[1])
 
 
+def _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, sq, sk, red):
+    """The mixer's backward under ``cfg.linear_attn``: dq | dk | dv into ``dqkv`` from qkv and do alone (the chunk
+    states are rebuilt inside the call), then the inverse RoPE / QK-norm backward as after ``attn_bwd``."""
+    qd, kd = Hq * D, Hkv * D
+    F_.linear_attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], do, dqkv[:, :qd], dqkv[:, qd:qd + kd],
+                       dqkv[:, qd + kd:], B, T, Hq, Hkv, model.linear_attn_decays(qkv.device))
+    _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, sq, sk, red)
+
+
 class _LayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, model, i):
@@ -346,7 +360,12 @@ class _LayerFn(torch.autograd.Function):
         # document mask: the forward's bounds (window folded in) replace the window, and stay for the backward
         bounds = model._cur_bounds
         window = 0 if bounds is not None else cfg.sliding_window or 0
-        if model.cp is not None:      # context parallel: local queries against the group's gathered K | V
+        if cfg.linear_attn:           # the linear-time mixer in softmax attention's place: no lse, nothing else kept
+            raw = _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn)
+            lse = aux = None
+            o = F_.linear_attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
+                                   model.linear_attn_decays(qkv.device))
+        elif model.cp is not None:    # context parallel: local queries against the group's gathered K | V
             o, lse, aux, raw = _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, rt.seed, qkn, sink)
         else:
             raw = _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn)
@@ -436,6 +455,9 @@ class _LayerFn(torch.autograd.Function):
         if model.cp is not None:      # aux: the gathered K | V of the forward
             _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed, qkn, raw,
                          s[nb] if qkn else None, s[nb + 1] if qkn else None, red, sink, s[-1])
+        elif cfg.linear_attn:
+            _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, s[nb] if qkn else None,
+                             s[nb + 1] if qkn else None, red)
         else:
             dsink = F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                                 dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
@@ -688,6 +710,8 @@ def _layer_backward_recompute(ctx, dx2):
     if model.cp is not None:
         _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed, qkn, raw, sq, sk, red,
                      sink, s[-1])
+    elif cfg.linear_attn:
+        _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, sq, sk, red)
     else:
         dsink = F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                             dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
@@ -888,6 +912,13 @@ class MistralLM(nn.Module):
         key = (str(device), T)
         if key not in self._rope:
             self._rope[key] = ref.rope_tables(T, self.cfg.head_dim, self.cfg.rope_theta, device)
+        return self._rope[key]
+
+    def linear_attn_decays(self, device):
+        """fp32 [kv_heads] log2 of the fixed decays of ``cfg.linear_attn`` (``ref.linear_attn_log2_gamma``)."""
+        key = ("log2_gamma", str(device))
+        if key not in self._rope:
+            self._rope[key] = ref.linear_attn_log2_gamma(self.cfg.kv_heads, device)
         return self._rope[key]
 
     def num_params(self):

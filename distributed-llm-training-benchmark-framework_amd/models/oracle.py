@@ -187,7 +187,18 @@ class OracleMistral(nn.Module):
             q, k = _rope(q, cos, sin), _rope(k, cos, sin)
             k = k.repeat_interleave(H // Hkv, 1)
             v = v.repeat_interleave(H // Hkv, 1)
-            if cfg.sliding_window or cfg.doc_eos_id is not None or cfg.attn_sinks or cfg.attn_softcap:
+            if cfg.linear_attn:
+                # the quadratic form of fixed-decay linear attention: no softmax, the decay mask gamma^(i - j) with
+                # one gamma per KV head and RetNet's row normaliser r[i] = sqrt((1 - gamma) / (1 - gamma^(i + 1)))
+                # (gamma = 2^log2_gamma of the fp32 schedule the kernels are handed)
+                from ..ops import ref
+                lg = ref.linear_attn_log2_gamma(Hkv, idx.device).to(q.dtype).repeat_interleave(H // Hkv) * math.log(2.0)
+                i = torch.arange(T, device=idx.device, dtype=q.dtype)
+                diff = (i[:, None] - i[None, :]).clamp(min=0)
+                mask = torch.where(i[:, None] >= i[None, :], torch.exp(lg.view(H, 1, 1) * diff), torch.zeros_like(diff))
+                r = torch.sqrt(torch.expm1(lg.view(H, 1, 1)) / torch.expm1(lg.view(H, 1, 1) * (i + 1).view(1, T, 1)))
+                o = ((q @ k.transpose(-1, -2)) * (mask * r / math.sqrt(hd))) @ v
+            elif cfg.sliding_window or cfg.doc_eos_id is not None or cfg.attn_sinks or cfg.attn_softcap:
                 i = torch.arange(T, device=idx.device)
                 band = (i[None, :] <= i[:, None]).expand(B, 1, T, T)
                 if cfg.sliding_window:      # band mask: query i sees keys i - W < j <= i

@@ -851,6 +851,34 @@ def attn_bwd(q, k, v, o, do, lse, aux, dq, dk, dv, B, T, Hq, Hkv, scale, causal,
     return ds
 
 
+def linear_attn_log2_gamma(Hkv, device=None):
+    """fp32 [Hkv] ``log2(gamma_g)`` of the RetNet decay schedule ``gamma_g = 1 - 2^(-5 - 8 g / Hkv)``."""
+    return ref.linear_attn_log2_gamma(Hkv, device)
+
+
+def linear_attn_fwd(q, k, v, B, T, Hq, Hkv, log2_gamma, o_out=None):
+    """Fixed-decay linear attention (csrc/linear_attn.hip; the contract is :func:`ref.linear_attn_fwd`):
+    ``o[i] = r[g,i] / sqrt(D) * sum_{j <= i} gamma_g^(i-j) (q[i] . k[j]) v[j]`` for query head h of KV group
+    ``g = h // (Hq // Hkv)``, ``r[g,i] = sqrt((1 - gamma_g) / (1 - gamma_g^(i+1)))``.  q / k / v: strided views as for
+    :func:`attn_fwd`; ``log2_gamma``: fp32 [Hkv], strictly negative (checked for a CPU tensor only: a device tensor is
+    not read on the host; :func:`linear_attn_log2_gamma` is negative by construction); D in {64, 128}, T a multiple of 64.  Returns o [B*T, Hq*D]
+    (``o_out`` if given); there is no lse and nothing else to keep for the backward."""
+    ref.check_linear_attn(q, B, T, Hq, Hkv, log2_gamma)
+    if _gpu(q):
+        return ext().linear_attn_fwd(q, k, v, log2_gamma, B, T, Hq, Hkv, o_out)
+    return _into(o_out, ref.linear_attn_fwd(q, k, v, B, T, Hq, Hkv, log2_gamma))
+
+
+def linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, log2_gamma):
+    """dq / dk / dv (views of the fused dqkv) of :func:`linear_attn_fwd` from q, k, v and do alone: the chunk
+    states are rebuilt, the group's query heads are summed in index order, no atomics."""
+    ref.check_linear_attn(q, B, T, Hq, Hkv, log2_gamma)
+    if _gpu(q):
+        ext().linear_attn_bwd(q, k, v, do, dq, dk, dv, log2_gamma, B, T, Hq, Hkv)
+    else:
+        ref.linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, log2_gamma)
+
+
 # ------------------------------------------------------------------------------ linear
 # Own MFMA GEMM (csrc/gemm_rs.hip, register-staged, software-pipelined) for the per-layer NT products
 # C[M, N] = A[M, K] B[N, K]^T (+ bias) where it beats the tuned hipBLASLt solution: the shapes, tile

@@ -636,6 +636,104 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, T, Hq, Hkv, scale, causal, p, s
     return attn_sink_bwd(_f(lse).view(B, Hq, Tq), delta.squeeze(-1), sink)
 
 
+# ------------------------------------------------------------------------------ linear attention
+# Fixed-decay linear attention in the chunked form of csrc/linear_attn.hip (the contract of its kernels):
+#   o[i] = r[g,i] scale sum_{j <= i} gamma_g^(i-j) (q[i] . k[j]) v[j],  scale = 1 / sqrt(D),
+#   r[g,i] = sqrt((1 - gamma_g) / (1 - gamma_g^(i+1))),  g = h // (Hq // Hkv)
+# with T cut into chunks of LINEAR_ATTN_CHUNK rows: the decayed score tile of a chunk, the decayed V (dO) operand of
+# a state product and the running state a chunk multiplies are each rounded to the 16-bit format once; everything
+# else is fp32 (fp64 inputs stay fp64 and round nowhere).
+LINEAR_ATTN_CHUNK = 64
+
+
+def linear_attn_log2_gamma(Hkv, device=None):
+    """fp32 [Hkv]: log2 of the RetNet decays gamma_g = 1 - 2^(-5 - 8 g / Hkv) (at Hkv = 8: 1 - 2^-5 .. 1 - 2^-12)."""
+    g = torch.arange(Hkv, dtype=torch.float64)
+    return (torch.log1p(-torch.exp2(-5.0 - 8.0 * g / Hkv)) / math.log(2.0)).float().to(device)
+
+
+def check_linear_attn(q, B, T, Hq, Hkv, log2_gamma):
+    if Hq % Hkv:
+        raise ValueError(f"linear_attn: Hq % Hkv, got Hq {Hq}, Hkv {Hkv}")
+    D = q.shape[1] // Hq
+    if D not in (64, 128) or T % LINEAR_ATTN_CHUNK:
+        raise ValueError(f"linear_attn: needs D in {{64,128}} and T % {LINEAR_ATTN_CHUNK} == 0, got D {D}, T {T}")
+    if log2_gamma.dtype != torch.float32 or log2_gamma.numel() != Hkv:
+        raise ValueError("linear_attn: log2_gamma must be an fp32 [Hkv] tensor")
+    # 0 < gamma < 1: gamma = 1 makes the row normaliser 0 / 0 and gamma > 1 grows without bound.  A device tensor is
+    # the caller's to keep strictly negative (reading it here would synchronise, and break a graph capture)
+    if not log2_gamma.is_cuda and not bool((log2_gamma < 0).all()):
+        raise ValueError("linear_attn: log2_gamma must be strictly negative (0 < gamma < 1)")
+    return D
+
+
+def _la_setup(q, k, v, B, T, Hq, Hkv, log2_gamma):
+    """Chunked views [B, Hkv, (G,) nc, C, D], the rounding of an MFMA operand and the decay tables (per KV head)."""
+    D = check_linear_attn(q, B, T, Hq, Hkv, log2_gamma)
+    C, G, nc = LINEAR_ATTN_CHUNK, Hq // Hkv, T // LINEAR_ATTN_CHUNK
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    rd = (lambda t: t) if q.dtype == torch.float64 else (lambda t: t.to(q.dtype).to(ct))
+    l2g = log2_gamma.to(q.device, ct).view(Hkv, 1)
+    a = torch.arange(C, device=q.device, dtype=ct)
+    ln2 = math.log(2.0)
+    pos = torch.arange(1, T + 1, device=q.device, dtype=ct)
+    t = {"rs": (torch.sqrt(torch.expm1(l2g * ln2) / torch.expm1(l2g * pos * ln2)) / math.sqrt(D)).view(Hkv, nc, C),
+         "M": torch.where(a[:, None] >= a[None, :], torch.exp2(l2g.view(Hkv, 1, 1) * (a[:, None] - a[None, :]).clamp(min=0)),
+                          torch.zeros((), device=q.device, dtype=ct)),           # [Hkv, C, C]
+         "din": torch.exp2(l2g * (a + 1)), "dout": torch.exp2(l2g * (C - 1 - a)),   # [Hkv, C]
+         "gC": torch.exp2(l2g * C).view(1, Hkv, 1, 1)}
+    qh = q.to(ct).reshape(B, nc, C, Hkv, G, D).permute(0, 3, 4, 1, 2, 5)
+    kh = k.to(ct).reshape(B, nc, C, Hkv, D).permute(0, 3, 1, 2, 4)
+    vh = v.to(ct).reshape(B, nc, C, Hkv, D).permute(0, 3, 1, 2, 4)
+    return D, C, G, nc, rd, t, qh, kh, vh
+
+
+def _la_scan(local, gC, rd, reverse):
+    """out[c] = the running state before chunk c joins it, rounded; s = gC s + local[c] (chunks along dim 2)."""
+    nc = local.shape[2]
+    s = torch.zeros_like(local[:, :, 0])
+    out = torch.empty_like(local)
+    for c in (range(nc - 1, -1, -1) if reverse else range(nc)):
+        out[:, :, c] = rd(s)
+        s = gC * s + local[:, :, c]
+    return out
+
+
+def linear_attn_fwd(q, k, v, B, T, Hq, Hkv, log2_gamma):
+    """q [B*T, Hq*D], k / v [B*T, Hkv*D] (strided views are fine) -> o [B*T, Hq*D] in q's dtype."""
+    D, C, G, nc, rd, t, qh, kh, vh = _la_setup(q, k, v, B, T, Hq, Hkv, log2_gamma)
+    local = torch.einsum("bgcnd,bgcne->bgcde", kh, rd(vh * t["dout"].view(1, Hkv, 1, C, 1)))
+    S = _la_scan(local, t["gC"], rd, False)
+    P = rd(torch.einsum("bghcad,bgcnd->bghcan", qh, kh) * t["M"].view(1, Hkv, 1, 1, C, C))
+    o = torch.einsum("bghcan,bgcne->bghcae", P, vh) \
+        + t["din"].view(1, Hkv, 1, 1, C, 1) * torch.einsum("bghcad,bgcde->bghcae", qh, S)
+    o = o * t["rs"].view(1, Hkv, 1, nc, C, 1)
+    return o.permute(0, 3, 4, 1, 2, 5).reshape(B * T, Hq * D).to(q.dtype)
+
+
+def linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, log2_gamma):
+    """The gradients of :func:`linear_attn_fwd` into dq / dk / dv (views of a fused dqkv are fine); the states are
+    rebuilt, nothing of the forward is needed."""
+    D, C, G, nc, rd, t, qh, kh, vh = _la_setup(q, k, v, B, T, Hq, Hkv, log2_gamma)
+    doh = do.to(qh.dtype).reshape(B, nc, C, Hkv, G, D).permute(0, 3, 4, 1, 2, 5)
+    M = t["M"].view(1, Hkv, 1, 1, C, C)
+    rs = t["rs"].view(1, Hkv, 1, nc, C, 1)
+    din = t["din"].view(1, Hkv, 1, 1, C, 1)
+    dout = t["dout"].view(1, Hkv, 1, C, 1)
+    S = _la_scan(torch.einsum("bgcnd,bgcne->bgcde", kh, rd(vh * dout)), t["gC"], rd, False)
+    dP = torch.einsum("bghcae,bgcne->bghcan", doh, vh)
+    dqh = rs * (torch.einsum("bghcan,bgcnd->bghcad", rd(dP * M), kh)
+                + din * torch.einsum("bghcae,bgcde->bghcad", doh, S))
+    dS = _la_scan(torch.einsum("bghcad,bghcae->bgcde", qh, rd(doh * (rs * din))), t["gC"], rd, True)
+    f = M * rs                                                          # rs of the query row, a
+    Sm = rd(torch.einsum("bghcad,bgcnd->bghcan", qh, kh) * f)
+    dkh = torch.einsum("bghcan,bghcad->bgcnd", rd(dP * f), qh) + dout * torch.einsum("bgcde,bgcne->bgcnd", dS, vh)
+    dvh = torch.einsum("bghcan,bghcae->bgcne", Sm, doh) + dout * torch.einsum("bgcnd,bgcde->bgcne", kh, dS)
+    dq.copy_(dqh.permute(0, 3, 4, 1, 2, 5).reshape(B * T, Hq * D).to(dq.dtype))
+    dk.copy_(dkh.permute(0, 2, 3, 1, 4).reshape(B * T, Hkv * D).to(dk.dtype))
+    dv.copy_(dvh.permute(0, 2, 3, 1, 4).reshape(B * T, Hkv * D).to(dv.dtype))
+
+
 # ------------------------------------------------------------------------------ mixture of experts
 # Top-k routing with a fixed capacity (csrc/moe.hip).  N token rows, E experts, K choices per token, C slots per
 # expert.  Index tensors are int32: expert / slot [N, K], src / src_k [E * C], counts [E]; slot -1 = dropped

@@ -127,6 +127,9 @@ class ContextParallel:
         if cfg is None or not getattr(cfg, "causal", False) or not hasattr(model, "rope"):
             raise ValueError("context parallelism needs a causal Mistral-shape tier (M7B, M7B_narrow, mtiny); the "
                              "TinyGPT tiers attend non-causally, with dropout and learned positions")
+        if self.cp > 1 and getattr(cfg, "linear_attn", False):
+            raise ValueError("--linear-attn (linear_attn) is not supported together with --context-parallel: the chunk "
+                             "state is not passed between ranks")
         model.cp = self if self.cp > 1 else None
         return model
 

@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Fixed-decay linear attention (csrc/linear_attn.hip) against the full-causal softmax attention kernels at the M7B
+head shape (Hq 32, Hkv 8, D 128, bf16, B 1), forward and backward, in one process.
+
+Per sequence length the four calls (linear fwd, softmax fwd, linear bwd, softmax bwd) alternate over ``--rounds``
+rounds of ``--iters`` calls after a warm-up round; each call of a round takes the next buffer set of a ring whose
+operands together exceed ``--ring-mib`` (larger than the 256 MiB last-level cache), so no call finds its inputs
+cached by the one before.  The median round is reported with its min .. max.  No ratio is a pass condition; the file
+records what was measured, including the first measured T at which the linear mixer is below softmax attention.
+
+    python scripts/bench_linear_attn.py --out profiles/linear_attn.txt
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import dltb  # noqa: E402,F401
+from dltb.ops import functional as F_  # noqa: E402
+from dltb.ops._ext import ext  # noqa: E402
+
+
+def timeit(fn, iters):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    s.record()
+    for i in range(iters):
+        fn(i)
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters * 1e3   # us
+
+
+def run(T, iters, rounds, ring_mib, emit, B=1, Hq=32, Hkv=8, D=128):
+    C, dev = ext(), "cuda"
+    qd, kd = Hq * D, Hkv * D
+    per_set = B * T * (qd + 2 * kd + qd) * 2
+    n = max(2, -(-ring_mib * 2 ** 20 // per_set))
+    g = torch.Generator(device=dev).manual_seed(0)
+    l2g = F_.linear_attn_log2_gamma(Hkv, dev)
+    scale = D ** -0.5
+    sets = []
+    for _ in range(n):
+        qkv = torch.randn(B * T, qd + 2 * kd, device=dev, dtype=torch.bfloat16, generator=g)
+        do = torch.randn(B * T, qd, device=dev, dtype=torch.bfloat16, generator=g)
+        q, k, v = qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:]
+        sets.append((q, k, v, do))
+    o = torch.empty(B * T, qd, device=dev, dtype=torch.bfloat16)
+    dqkv = torch.empty(B * T, qd + 2 * kd, device=dev, dtype=torch.bfloat16)
+    dq, dk, dv = dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:]
+    so, lse = C.attn_fwd(*sets[0][:3], None, B, T, Hq, Hkv, scale, True, 0.0)   # any o / lse: the time does not depend on them
+
+    def lin_fwd(i):
+        q, k, v, _ = sets[i % n]
+        C.linear_attn_fwd(q, k, v, l2g, B, T, Hq, Hkv, o)
+
+    def soft_fwd(i):
+        q, k, v, _ = sets[i % n]
+        C.attn_fwd(q, k, v, None, B, T, Hq, Hkv, scale, True, 0.0, o)
+
+    def lin_bwd(i):
+        q, k, v, do = sets[i % n]
+        C.linear_attn_bwd(q, k, v, do, dq, dk, dv, l2g, B, T, Hq, Hkv)
+
+    def soft_bwd(i):
+        q, k, v, do = sets[i % n]
+        C.attn_bwd(q, k, v, so, do, lse, None, dq, dk, dv, B, T, Hq, Hkv, scale, True, 0.0)
+
+    fns = {"linear fwd": lin_fwd, "softmax fwd": soft_fwd, "linear bwd": lin_bwd, "softmax bwd": soft_bwd}
+    times = {key: [] for key in fns}
+    for r in range(rounds + 1):                 # round 0 warms up
+        for key, fn in fns.items():
+            us = timeit(fn, iters)
+            if r:
+                times[key].append(us)
+    med = {key: sorted(t)[len(t) // 2] for key, t in times.items()}
+    emit(f"T {T:6d}  ring {n} sets of {per_set / 2 ** 20:.0f} MiB")
+    for key in fns:
+        emit(f"    {key:12s} {med[key]:10.1f} us  ({min(times[key]):.1f} .. {max(times[key]):.1f})")
+    emit(f"    linear / softmax: fwd {med['linear fwd'] / med['softmax fwd']:.3f}  bwd "
+         f"{med['linear bwd'] / med['softmax bwd']:.3f}  fwd + bwd "
+         f"{(med['linear fwd'] + med['linear bwd']) / (med['softmax fwd'] + med['softmax bwd']):.3f}")
+    del sets
+    torch.cuda.empty_cache()
+    return (med["linear fwd"] + med["linear bwd"]) / (med["softmax fwd"] + med["softmax bwd"])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seq-lens", default="4096,16384,32768")
+    ap.add_argument("--iters", type=int, default=8)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--ring-mib", type=int, default=320)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+    emit("# scripts/bench_linear_attn.py: fixed-decay linear attention against full-causal softmax attention, M7B head")
+    emit(f"# shape (B 1, Hq 32, Hkv 8, D 128, bf16), {torch.cuda.get_device_name(0)}; medians of {a.rounds} interleaved "
+         f"rounds of {a.iters} calls")
+    emit(f"# (min .. max), operand rings of more than {a.ring_mib} MiB.  The linear backward includes rebuilding the states.")
+    cross = None
+    for T in (int(t) for t in a.seq_lens.split(",")):
+        ratio = run(T, a.iters, a.rounds, a.ring_mib, emit)
+        if cross is None and ratio < 1.0:
+            cross = T
+    emit("# linear fwd + bwd below softmax fwd + bwd from the measured T = " + (str(cross) if cross else "none measured"))
+    emit("# end-to-end step time under --linear-attn: not measured")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
