@@ -209,6 +209,26 @@ void dltb_linear_attn_bwd(const void* q, const void* k, const void* v, const voi
                           const float* l2g, float* local, void* state, long qs, long ks, long vs, long dos, long dqs,
                           long dks, long dvs, int B, int T, int Hq, int Hkv, int D, float scale, hipStream_t st);
 
+// ---- linear_attn_gate.hip: the same with data-dependent scalar decays, o[i] = scale sum_{j<=i} exp2(L[i] - L[j])
+// (q[i].k[j]) v[j], L the running sum of l = log2 sigmoid(xn . Wg[g] + bias[g]) along a row; no row normaliser.
+// gate_fwd: xn [B T, d] and wg [Hkv, d] 16-bit contiguous, bias fp32 [Hkv] -> z and cum (the prefix sum of l inside
+// each chunk), fp32 [B T, Hkv].  gated_fwd / gated_bwd: dltb_linear_attn_fwd / _bwd with cum in l2g's place; the
+// backward also writes gq [B T, Hq] = dq . q and gk [B T, Hkv] = dk . k from its fp32 accumulators.  gate_bwd:
+// dz [B T, Hkv] = (suffix sum along each row of sum_{h in g} gq - gk) * (1 - sigmoid(z + bias)) (z null: the suffix
+// sum itself), then dxn [B T, d] += dz wg in place, rounded once (dxn null: skipped).
+bool dltb_linear_attn_gate_supported(int T, int d, int Hkv);
+void dltb_linear_attn_gate_fwd(const void* xn, const void* wg, const float* bias, float* z, float* cum, int B, int T,
+                               int d, int Hkv, hipStream_t st);
+void dltb_linear_attn_gate_bwd(const float* gq, const float* gk, const float* z, const float* bias, const void* wg,
+                               float* dz, void* dxn, int B, int T, int d, int Hq, int Hkv, hipStream_t st);
+void dltb_linear_attn_gated_fwd(const void* q, const void* k, const void* v, void* o, const float* cum, float* local,
+                                void* state, long qs, long ks, long vs, long os, int B, int T, int Hq, int Hkv, int D,
+                                float scale, hipStream_t st);
+void dltb_linear_attn_gated_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk,
+                                void* dv, const float* cum, float* gq, float* gk, float* local, void* state, long qs,
+                                long ks, long vs, long dos, long dqs, long dks, long dvs, int B, int T, int Hq, int Hkv,
+                                int D, float scale, hipStream_t st);
+
 // ---- batched column reductions (colreduce.hip)
 #ifndef DLTB_LAUNCHER_TYPES   // types once (launchers_f16.h repeats only the declarations)
 #define DLTB_LAUNCHER_TYPES

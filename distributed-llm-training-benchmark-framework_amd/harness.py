@@ -131,6 +131,11 @@ def build_parser():
                         "lightning form, one decay 1 - 2^(-5 - 8 g / kv_heads) per KV head, a [head_dim, head_dim] "
                         "state, linear in the sequence length) in softmax attention's place; no parameter; not with "
                         "--context-parallel, --sliding-window, --doc-len, --attn-sinks or --attn-softcap; default: off")
+    p.add_argument("--linear-attn-gate", action="store_true",
+                   help="with --linear-attn: data-dependent decays (the Mamba-2 / gated-RetNet form), per token and KV "
+                        "head the scalar sigmoid(xn . Wg[g] + b_g) in the fixed decay's place and no row normaliser; one "
+                        "zero-initialised [kv_heads, n_embd] weight per layer, b_g fixed so that training starts from "
+                        "the --linear-attn decays; default: off")
     p.add_argument("--attn-softcap", type=float, default=0.0, metavar="C",
                    help="causal tiers: attention logit soft-capping, every score x becomes C * tanh(x / C) before the "
                         "softmax (Gemma-2 uses 50), in capped instantiations of the three attention kernels; not "
@@ -322,9 +327,11 @@ def check_fp8_linear(on, mcfg, tier, loss_scaling=False):
     mcfg.validate()
 
 
-def check_linear_attn(on, mcfg, tier, cp=1):
+def check_linear_attn(on, mcfg, tier, cp=1, gate=False):
     """ValueError when ``--linear-attn`` is set for a tier or a job it does not cover (``mcfg`` carries the job's other
-    attention switches by now); sets it on ``mcfg``."""
+    attention switches by now), or ``--linear-attn-gate`` (``gate``) without it; sets them on ``mcfg``."""
+    if gate and not on:
+        raise ValueError("--linear-attn-gate needs --linear-attn: it gates the decays of the linear-attention mixer")
     if not on:
         return
     if not mcfg.causal:
@@ -334,6 +341,7 @@ def check_linear_attn(on, mcfg, tier, cp=1):
         raise ValueError("--linear-attn is not supported together with --context-parallel: the chunk state is not "
                          "passed between ranks")
     mcfg.linear_attn = True
+    mcfg.linear_attn_gate = bool(gate)
     mcfg.validate()
 
 
@@ -514,7 +522,8 @@ def train(args):
                            args.tier)
         check_final_softcap(getattr(args, "final_softcap", 0.0), mcfg, args.tier)
         check_lm_z_loss(getattr(args, "lm_z_loss_coef", 0.0), mcfg, args.tier)
-        check_linear_attn(bool(getattr(args, "linear_attn", False)), mcfg, args.tier, cp_n)
+        check_linear_attn(bool(getattr(args, "linear_attn", False)), mcfg, args.tier, cp_n,
+                          bool(getattr(args, "linear_attn_gate", False)))
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -729,6 +738,7 @@ def train(args):
             "sandwich_norm": bool(mcfg.sandwich_norm), "ffn_act": str(mcfg.ffn_act),
             "fp8_linear": bool(mcfg.fp8_linear),
             "linear_attn": bool(mcfg.linear_attn),
+            "linear_attn_gate": bool(mcfg.linear_attn_gate),
             "attn_softcap": float(mcfg.attn_softcap),
             "final_softcap": float(mcfg.final_softcap),
             "lm_z_loss_coef": float(mcfg.lm_z_loss_coef),
@@ -845,7 +855,7 @@ def main(argv=None):
             cfg0.sliding_window = args.sliding_window
             cfg0.doc_eos_id = None if args.doc_len is None else cfg0.vocab_size - 1
             cfg0.attn_sinks, cfg0.attn_softcap = bool(args.attn_sinks), float(args.attn_softcap)
-        check_linear_attn(args.linear_attn, cfg0, args.tier, args.context_parallel)
+        check_linear_attn(args.linear_attn, cfg0, args.tier, args.context_parallel, args.linear_attn_gate)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

@@ -93,6 +93,12 @@ class ModelConfig:
     # a [head_dim, head_dim] state per KV head (csrc/linear_attn.hip).  No parameter, no lse.  Causal only; not with
     # sliding_window, doc_eos_id, attn_sinks, attn_softcap or dropout.
     linear_attn: bool = False
+    # data-dependent decay gates for linear_attn (the Mamba-2 / gated-RetNet form): per token and KV head a scalar decay
+    # a[t,g] = sigmoid(xn[t] . Wg[g] + b_g) replaces gamma_g, o[i] = 1 / sqrt(head_dim) * sum_{j <= i} (prod_{j < s <= i}
+    # a[s,g]) (q[i] . k[j]) v[j], without the row normaliser; b_g = ln(gamma_g / (1 - gamma_g)) is fixed, so the zero-
+    # initialised parameter self_attn.decay_gate.weight [kv_heads, n_embd] (the last of a layer) starts from the RetNet
+    # decays (csrc/linear_attn_gate.hip).  Needs linear_attn and n_embd % 8 == 0.
+    linear_attn_gate: bool = False
 
     def __post_init__(self):
         self.validate()
@@ -169,6 +175,16 @@ class ModelConfig:
                              (self.head_dim not in (64, 128), f"needs head_dim 64 or 128, got {self.head_dim}")):
                 if bad:
                     raise ValueError(f"--linear-attn (linear_attn, fixed-decay linear attention) {why}")
+        if not isinstance(self.linear_attn_gate, bool):
+            raise ValueError(f"linear_attn_gate must be a bool, got {self.linear_attn_gate!r}")
+        if self.linear_attn_gate and not self.linear_attn:
+            raise ValueError("--linear-attn-gate (linear_attn_gate, data-dependent decay gates) needs --linear-attn "
+                             "(linear_attn)")
+        if self.linear_attn_gate and (self.n_embd % 8 or self.kv_heads > 64
+                                      or self.kv_heads * (2 * self.n_embd + 256) > 160 * 1024):
+            raise ValueError("--linear-attn-gate (linear_attn_gate) needs n_embd % 8 == 0, kv_heads <= 64 and "
+                             "kv_heads * (2 * n_embd + 256) <= 160 KiB (the gate weight is staged in LDS), got n_embd "
+                             f"{self.n_embd}, kv_heads {self.kv_heads}")
         k, cf = self.moe_top_k, self.moe_capacity_factor
         if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4):
             raise ValueError(f"moe_top_k must be 1, 2 or 4, got {k!r}")
@@ -242,6 +258,8 @@ class ModelConfig:
             per_block += 2 * d
         if self.attn_sinks:      # one sink logit per query head
             per_block += self.n_head
+        if self.linear_attn_gate:    # the decay gate's weight
+            per_block += self.kv_heads * d
         head = 0 if self.tie_embeddings else V * d
         return V * d + L * per_block + d + head
 
@@ -261,7 +279,7 @@ class ModelConfig:
         (2 * C/2 * head_dim each per query head, C = ``ops.ref.LINEAR_ATTN_CHUNK``), the query by the state (2 * head_dim^2 per query head) and
         builds the state (2 * head_dim^2 per KV head); times 3 for forward + backward,
         ``attn = 6 * L * (d * (C + head_dim) + kv_dim * head_dim)``.  The states the backward rebuilds are not
-        counted, and no T x T product is."""
+        counted, and no T x T product is.  ``linear_attn_gate`` adds the gate's projection, ``6 * L * n_embd * kv_heads``."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d
@@ -280,6 +298,8 @@ class ModelConfig:
         if self.linear_attn:
             from ..ops.ref import LINEAR_ATTN_CHUNK as C      # the kernels' chunk (csrc/linear_attn.hip kC)
             attn = 6.0 * L * (d * (C + self.head_dim) + self.kv_heads * self.head_dim * self.head_dim)
+            if self.linear_attn_gate:
+                attn += 6.0 * L * d * self.kv_heads
         return 6.0 * n_mat + attn
 
 

@@ -51,6 +51,15 @@ would call ``attn_fwd`` / ``attn_bwd``: fixed-decay linear attention on the same
 QK-norm + RoPE), one decay per KV head.  There is no lse and the backward rebuilds the chunk states, so both recompute
 modes keep ``o`` for the mixer and never re-run it.  ``ContextParallel.attach`` refuses such a model.
 
+With ``cfg.linear_attn_gate`` the decays are data-dependent: ``self_attn.decay_gate.weight`` [kv_heads, n_embd], the
+LAST parameter of a layer (the sinks' place; a config never has both), projects the pre-attention norm output to one
+logit per token and KV head (``linear_attn_gate_fwd``: z and the chunk prefix sums ``cum`` of log2 sigmoid(z + b_g),
+csrc/linear_attn_gate.hip), and the mixer's two calls take ``cum=``.  z and cum (fp32, 8 bytes per token and KV head)
+are kept in every recompute mode.  The backward's mixer call returns the gate gradient's two row dots; once the qkv
+product's data gradient exists, ``linear_attn_gate_bwd`` forms dz from them and adds its term to that gradient in
+place, and the weight gradient goes through the MoE router's dense kernel.  Engines treat the weight like the
+router's: AdamW updates it (Muon leaves it to its inner AdamW) and ``fp8_linear`` leaves its product 16-bit.
+
 With ``cfg.sandwich_norm`` every sublayer's output goes through its own RMSNorm before it joins the residual stream,
 ``x1 = x + RMSNorm(a; self_attn.out_norm)`` and ``x2 = x1 + RMSNorm(m; mlp.out_norm)`` (m: the dense FFN's output or the
 MoE combine), on top of the two pre-norms.  The two [n_embd] weights sit in the layer's parameter list after the
@@ -79,7 +88,7 @@ class _RMSNorm(nn.Module):
 
 
 class _Attn(nn.Module):
-    def __init__(self, d, kvd, qk_norm_dim=None, n_sinks=None):
+    def __init__(self, d, kvd, qk_norm_dim=None, n_sinks=None, n_gates=None):
         super().__init__()
         self.qkv_proj = nn.Linear(d, d + 2 * kvd, bias=False)
         self.o_proj = nn.Linear(d, d, bias=False)
@@ -88,6 +97,8 @@ class _Attn(nn.Module):
             self.k_norm = _RMSNorm(qk_norm_dim)
         if n_sinks:             # attention sinks: one raw logit per query head
             self.sinks = nn.Parameter(torch.zeros(n_sinks))
+        if n_gates:             # linear attention's decay gate: one row per KV head, zeros (MistralLM.__init__)
+            self.decay_gate = nn.Linear(d, n_gates, bias=False)
 
 
 class _MLP(nn.Module):
@@ -112,9 +123,11 @@ class MistralLayer(nn.Module):
         d = cfg.n_embd
         self.input_layernorm = _RMSNorm(d)
         self.self_attn = _Attn(d, cfg.kv_heads * cfg.head_dim, cfg.head_dim if cfg.qk_norm else None,
-                               cfg.n_head if cfg.attn_sinks else None)
+                               cfg.n_head if cfg.attn_sinks else None,
+                               cfg.kv_heads if cfg.linear_attn_gate else None)
         self.qk_norm = cfg.qk_norm
         self.attn_sinks = cfg.attn_sinks
+        self.linear_attn_gate = cfg.linear_attn_gate
         self.sandwich_norm = cfg.sandwich_norm
         self.post_attention_layernorm = _RMSNorm(d)
         self.mlp = _MoE(d, cfg.ffn_dim, cfg.n_experts) if cfg.n_experts else _MLP(d, cfg.ffn_dim)
@@ -124,7 +137,8 @@ class MistralLayer(nn.Module):
 
     def param_list(self):
         # the QK-norm weights, then the sandwich norms' pair and then the sinks come last, so the dense (4, 5) and MoE
-        # (4, 5 + 2e, 6 + 2e) indices hold with them
+        # (4, 5 + 2e, 6 + 2e) indices hold with them; linear attention's decay gate takes the sinks' place (a config
+        # never has both)
         tail = []
         if self.qk_norm:
             tail = [("self_attn.q_norm.weight", self.self_attn.q_norm.weight),
@@ -134,6 +148,8 @@ class MistralLayer(nn.Module):
                            ("mlp.out_norm.weight", self.mlp.out_norm.weight)]
         if self.attn_sinks:
             tail = tail + [("self_attn.sinks", self.self_attn.sinks)]
+        if self.linear_attn_gate:
+            tail = tail + [("self_attn.decay_gate.weight", self.self_attn.decay_gate.weight)]
         head = [("input_layernorm.weight", self.input_layernorm.weight),
                 ("self_attn.qkv_proj.weight", self.self_attn.qkv_proj.weight),
                 ("self_attn.o_proj.weight", self.self_attn.o_proj.weight),
@@ -171,8 +187,9 @@ class _EmbedFn(torch.autograd.Function):
 
 def _n_block_weights(cfg, ws):
     """How many of a layer's parameters ``ws`` come before its tail -- the QK-norm pair, then the sandwich norms'
-    pair, then the sinks -- that is the norms, projections and the FFN."""
-    return len(ws) - (2 if cfg.qk_norm else 0) - (2 if cfg.sandwich_norm else 0) - (1 if cfg.attn_sinks else 0)
+    pair, then the sinks or the decay gate -- that is the norms, projections and the FFN."""
+    return len(ws) - (2 if cfg.qk_norm else 0) - (2 if cfg.sandwich_norm else 0) \
+        - (1 if cfg.attn_sinks or cfg.linear_attn_gate else 0)
 
 
 def _attn_tail(cfg, ws):
@@ -331,13 +348,30 @@ def _cp_attn_bwd(model, qkv, kv, o, do, lses, dqkv, Hq, Hkv, D, window, bounds, 
         F_.reduce_partials(red, part[1], sk[0], sk[1])
 
 
-def _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, sq, sk, red):
+def _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, sq, sk, red, gate=None):
     """The mixer's backward under ``cfg.linear_attn``: dq | dk | dv into ``dqkv`` from qkv and do alone (the chunk
-    states are rebuilt inside the call), then the inverse RoPE / QK-norm backward as after ``attn_bwd``."""
+    states are rebuilt inside the call), then the inverse RoPE / QK-norm backward as after ``attn_bwd``.  ``gate``:
+    the kept (z, cum) of ``cfg.linear_attn_gate``; returns then the gate gradient's row dots (gq, gk) for
+    :func:`_gate_bwd`, taken on the q and k the mixer saw (after RoPE)."""
     qd, kd = Hq * D, Hkv * D
-    F_.linear_attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], do, dqkv[:, :qd], dqkv[:, qd:qd + kd],
-                       dqkv[:, qd + kd:], B, T, Hq, Hkv, model.linear_attn_decays(qkv.device))
+    g = F_.linear_attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], do, dqkv[:, :qd], dqkv[:, qd:qd + kd],
+                           dqkv[:, qd + kd:], B, T, Hq, Hkv, model.linear_attn_decays(qkv.device),
+                           cum=None if gate is None else gate[1])
     _rope_bwd(model, dqkv, T, Hq, Hkv, D, qkn, raw, sq, sk, red)
+    return g
+
+
+def _gate_fwd(model, h1, wg, B, T):
+    """(z, cum) of the decay gate on the pre-attention norm output ``h1``; both are kept in every recompute mode."""
+    return F_.linear_attn_gate_fwd(h1, wg, model.linear_attn_gate_bias(h1.device), B, T)
+
+
+def _gate_bwd(model, g, gate, wg, h1, dh1, slot, B, T):
+    """The decay gate's backward, after the qkv product's data gradient ``dh1`` exists: dz from the row dots ``g`` and
+    the kept z, its rank-kv_heads term added into ``dh1`` in place, and dWg = dz^T h1 into the gate's gradient slot
+    (the MoE router's dense weight-gradient kernel: fp32 [N, kv_heads] times 16-bit rows, fixed-order partials)."""
+    dz = F_.linear_attn_gate_bwd(g[0], g[1], gate[0], model.linear_attn_gate_bias(h1.device), wg, dh1, B, T)
+    F_.moe_router_wgrad(dz, h1, slot[0], slot[1], dense=True)
 
 
 class _LayerFn(torch.autograd.Function):
@@ -352,6 +386,7 @@ class _LayerFn(torch.autograd.Function):
         ws = rt.acquire(unit)
         (w_in, wqkv, wo, w_post) = ws[:4]
         nb, qkn, sink = _attn_tail(cfg, ws)      # (q weight, k weight) of QK-norm; the attention sinks
+        ctx.gate = None
         B, T = model._cur_bt
         Hq, Hkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
         _, h1, _, rstd1 = F_.norm_fwd(x, None, w_in, None, cfg.norm_eps, True)
@@ -363,8 +398,10 @@ class _LayerFn(torch.autograd.Function):
         if cfg.linear_attn:           # the linear-time mixer in softmax attention's place: no lse, nothing else kept
             raw = _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn)
             lse = aux = None
+            if cfg.linear_attn_gate:  # the decay gate (the layer's last parameter): z and cum, kept in every mode
+                ctx.gate = _gate_fwd(model, h1, ws[-1], B, T)
             o = F_.linear_attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
-                                   model.linear_attn_decays(qkv.device))
+                                   model.linear_attn_decays(qkv.device), cum=ctx.gate and ctx.gate[1])
         elif model.cp is not None:    # context parallel: local queries against the group's gathered K | V
             o, lse, aux, raw = _cp_attn_fwd(model, qkv, Hq, Hkv, D, window, bounds, rt.seed, qkn, sink)
         else:
@@ -456,8 +493,8 @@ class _LayerFn(torch.autograd.Function):
             _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed, qkn, raw,
                          s[nb] if qkn else None, s[nb + 1] if qkn else None, red, sink, s[-1])
         elif cfg.linear_attn:
-            _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, s[nb] if qkn else None,
-                             s[nb + 1] if qkn else None, red)
+            gdots = _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, s[nb] if qkn else None,
+                                     s[nb + 1] if qkn else None, red, ctx.gate)
         else:
             dsink = F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                                 dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
@@ -469,6 +506,9 @@ class _LayerFn(torch.autograd.Function):
         ctx.bounds = None
         F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
         dh1 = _lin_dgrad(model, unit, 1, dqkv, wqkv)
+        if ctx.gate is not None:
+            _gate_bwd(model, gdots, ctx.gate, ws[-1], h1, dh1, s[-1], B, T)
+            ctx.gate = None
         dx = F_.norm_bwd(dh1, x, w_in, None, rstd1, dx1, s[0][0], None, s[0][1], True, red=red)
         if shared is None:
             red.flush()
@@ -711,7 +751,7 @@ def _layer_backward_recompute(ctx, dx2):
         _cp_attn_bwd(model, qkv, aux, o, do, lse, dqkv, Hq, Hkv, D, window, ctx.bounds, rt.seed, qkn, raw, sq, sk, red,
                      sink, s[-1])
     elif cfg.linear_attn:
-        _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, sq, sk, red)
+        gdots = _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, sq, sk, red, ctx.gate)
     else:
         dsink = F_.attn_bwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], o, do, lse, aux,
                             dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:], B, T, Hq, Hkv,
@@ -723,9 +763,12 @@ def _layer_backward_recompute(ctx, dx2):
     ctx.bounds = None
     del qkv, aux, o, do, lse, raw
     F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
-    del h1
     dh1 = _lin_dgrad(model, unit, 1, dqkv, wqkv)
     del dqkv
+    if ctx.gate is not None:      # the kept z and cum; h1 is the rebuilt one, the forward's bit for bit
+        _gate_bwd(model, gdots, ctx.gate, ws[-1], h1, dh1, s[-1], B, T)
+        ctx.gate = None
+    del h1
     dx = F_.norm_bwd(dh1, x, w_in, None, rstd1, dx1, s[0][0], None, s[0][1], True, red=red)
     if shared is None:
         red.flush()
@@ -886,6 +929,9 @@ class MistralLM(nn.Module):
         for mod in self.modules():
             if isinstance(mod, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(mod.weight, mean=0.0, std=0.02)
+        if cfg.linear_attn_gate:    # a zero gate weight: every layer starts from the fixed schedule's decays
+            for layer in self.model.layers:
+                nn.init.zeros_(layer.self_attn.decay_gate.weight)
         self.rt = EAGER
         self.drop_p = 0.0
         self._rope = {}
@@ -919,6 +965,13 @@ class MistralLM(nn.Module):
         key = ("log2_gamma", str(device))
         if key not in self._rope:
             self._rope[key] = ref.linear_attn_log2_gamma(self.cfg.kv_heads, device)
+        return self._rope[key]
+
+    def linear_attn_gate_bias(self, device):
+        """fp32 [kv_heads] fixed offsets of ``cfg.linear_attn_gate`` (``ref.linear_attn_gate_bias``)."""
+        key = ("gate_bias", str(device))
+        if key not in self._rope:
+            self._rope[key] = ref.linear_attn_gate_bias(self.cfg.kv_heads, device)
         return self._rope[key]
 
     def num_params(self):

@@ -146,6 +146,9 @@ class OracleMistral(nn.Module):
                 layer.self_attn.k_norm = _RMSNorm(hd, cfg.norm_eps)
             if cfg.attn_sinks:      # one learned sink logit per query head
                 layer.self_attn.sinks = nn.Parameter(torch.zeros(cfg.n_head))
+            if cfg.linear_attn_gate:    # linear attention's decay gate, one row per KV head, zeros
+                layer.self_attn.decay_gate = nn.Linear(d, cfg.kv_heads, bias=False)
+                nn.init.zeros_(layer.self_attn.decay_gate.weight)
             layer.post_attention_layernorm = _RMSNorm(d, cfg.norm_eps)
             layer.mlp = nn.Module()
             if cfg.sandwich_norm:   # every sublayer's output through its own RMSNorm before the residual add
@@ -187,7 +190,17 @@ class OracleMistral(nn.Module):
             q, k = _rope(q, cos, sin), _rope(k, cos, sin)
             k = k.repeat_interleave(H // Hkv, 1)
             v = v.repeat_interleave(H // Hkv, 1)
-            if cfg.linear_attn:
+            if cfg.linear_attn_gate:
+                # the quadratic form of gated linear attention: per token and KV head the decay sigmoid(h . Wg[g] + b_g),
+                # the mask exp(L[i] - L[j]) with L the running sum of its logarithm along the row, no row normaliser
+                from ..ops import ref
+                zb = layer.self_attn.decay_gate(h) + ref.linear_attn_gate_bias(Hkv, idx.device).to(h.dtype)
+                L = torch.nn.functional.logsigmoid(zb).cumsum(1).transpose(1, 2).repeat_interleave(H // Hkv, 1)   # [B, H, T]
+                i = torch.arange(T, device=idx.device)
+                diff = (L[..., :, None] - L[..., None, :]).clamp(max=0)
+                mask = torch.where(i[:, None] >= i[None, :], torch.exp(diff), torch.zeros_like(diff))
+                o = ((q @ k.transpose(-1, -2)) * (mask / math.sqrt(hd))) @ v
+            elif cfg.linear_attn:
                 # the quadratic form of fixed-decay linear attention: no softmax, the decay mask gamma^(i - j) with
                 # one gamma per KV head and RetNet's row normaliser r[i] = sqrt((1 - gamma) / (1 - gamma^(i + 1)))
                 # (gamma = 2^log2_gamma of the fp32 schedule the kernels are handed)

@@ -856,23 +856,71 @@ def linear_attn_log2_gamma(Hkv, device=None):
     return ref.linear_attn_log2_gamma(Hkv, device)
 
 
-def linear_attn_fwd(q, k, v, B, T, Hq, Hkv, log2_gamma, o_out=None):
+def linear_attn_gate_bias(Hkv, device=None):
+    """fp32 [Hkv] ``b_g = ln(gamma_g / (1 - gamma_g))`` of the decay gate: the fixed, not learned offset with which a
+    zero gate weight gives the decays of :func:`linear_attn_log2_gamma`."""
+    return ref.linear_attn_gate_bias(Hkv, device)
+
+
+def linear_attn_gate_fwd(xn, wg, bias, B, T):
+    """The decay gate of ``--linear-attn-gate`` (csrc/linear_attn_gate.hip; the contract is
+    :func:`ref.linear_attn_gate_fwd`): ``z = xn Wg^T`` (16-bit operands, fp32) and ``cum``, the inclusive prefix sum
+    inside each chunk of 64 rows of ``l = log2 sigmoid(z + bias)``; both fp32 [B*T, Hkv].  ``cum`` is what
+    :func:`linear_attn_fwd` / :func:`linear_attn_bwd` take as ``cum=``; ``z`` is kept for :func:`linear_attn_gate_bwd`."""
+    if T % ref.LINEAR_ATTN_CHUNK or xn.shape[1] % 8 or wg.shape[1] != xn.shape[1] or bias.numel() != wg.shape[0]:
+        raise ValueError(f"linear_attn_gate: needs T % {ref.LINEAR_ATTN_CHUNK} == 0, n_embd % 8 == 0, wg [kv_heads, "
+                         f"n_embd] and bias [kv_heads], got T {T}, xn {tuple(xn.shape)}, wg {tuple(wg.shape)}")
+    if _gpu(xn):
+        z, cum = ext().linear_attn_gate_fwd(xn, wg, bias, B, T)
+        return z, cum
+    return ref.linear_attn_gate_fwd(xn, wg, bias, B, T)
+
+
+def linear_attn_gate_bwd(gq, gk, z, bias, wg, dxn, B, T):
+    """The gate's backward from the two row dots :func:`linear_attn_bwd` returns under ``cum=``: ``dl`` is the suffix
+    sum along each row of T tokens of ``sum_{h in g} gq - gk`` (one fixed order, no atomics), ``dz = dl (1 - a)`` with
+    ``a = sigmoid(z + bias)`` rebuilt from z; returns dz fp32 [B*T, Hkv] (``z`` None: dl).  With ``dxn`` [B*T, n_embd],
+    the data gradient of the qkv product, ``dxn = round(float(dxn) + dz Wg)`` in place.  The weight gradient is
+    ``moe_router_wgrad(dz, xn, ..., dense=True)``."""
+    if _gpu(gq):
+        return ext().linear_attn_gate_bwd(gq, gk, z, bias, wg, dxn, B, T)
+    return ref.linear_attn_gate_bwd(gq, gk, z, bias, wg, dxn, B, T)
+
+
+def linear_attn_fwd(q, k, v, B, T, Hq, Hkv, log2_gamma, o_out=None, cum=None):
     """Fixed-decay linear attention (csrc/linear_attn.hip; the contract is :func:`ref.linear_attn_fwd`):
     ``o[i] = r[g,i] / sqrt(D) * sum_{j <= i} gamma_g^(i-j) (q[i] . k[j]) v[j]`` for query head h of KV group
     ``g = h // (Hq // Hkv)``, ``r[g,i] = sqrt((1 - gamma_g) / (1 - gamma_g^(i+1)))``.  q / k / v: strided views as for
     :func:`attn_fwd`; ``log2_gamma``: fp32 [Hkv], strictly negative (checked for a CPU tensor only: a device tensor is
     not read on the host; :func:`linear_attn_log2_gamma` is negative by construction); D in {64, 128}, T a multiple of 64.  Returns o [B*T, Hq*D]
-    (``o_out`` if given); there is no lse and nothing else to keep for the backward."""
+    (``o_out`` if given); there is no lse and nothing else to keep for the backward.
+
+    ``cum`` (:func:`linear_attn_gate_fwd`): the gated form of csrc/linear_attn_gate.hip,
+    ``o[i] = 1 / sqrt(D) * sum_{j <= i} exp2(L[i] - L[j]) (q[i] . k[j]) v[j]`` with L the running sum of the gate's
+    log2 decays along a row; no row normaliser, and ``log2_gamma`` is not read."""
     ref.check_linear_attn(q, B, T, Hq, Hkv, log2_gamma)
+    if cum is None:
+        if _gpu(q):
+            return ext().linear_attn_fwd(q, k, v, log2_gamma, B, T, Hq, Hkv, o_out)
+        return _into(o_out, ref.linear_attn_fwd(q, k, v, B, T, Hq, Hkv, log2_gamma))
     if _gpu(q):
-        return ext().linear_attn_fwd(q, k, v, log2_gamma, B, T, Hq, Hkv, o_out)
-    return _into(o_out, ref.linear_attn_fwd(q, k, v, B, T, Hq, Hkv, log2_gamma))
+        return ext().linear_attn_fwd(q, k, v, log2_gamma, B, T, Hq, Hkv, o_out, cum)
+    return _into(o_out, ref.linear_attn_gated_fwd(q, k, v, B, T, Hq, Hkv, cum))
 
 
-def linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, log2_gamma):
+def linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, log2_gamma, cum=None):
     """dq / dk / dv (views of the fused dqkv) of :func:`linear_attn_fwd` from q, k, v and do alone: the chunk
-    states are rebuilt, the group's query heads are summed in index order, no atomics."""
+    states are rebuilt, the group's query heads are summed in index order, no atomics.
+
+    With ``cum`` the gated form; it then returns (gq [B*T, Hq], gk [B*T, Hkv]) in fp32, the row dots ``dq . q`` and
+    ``dk . k`` taken from the kernels' fp32 accumulators before dq and dk are rounded: the gate's gradient is their
+    difference, which cancels.  :func:`linear_attn_gate_bwd` takes them once the qkv product's data gradient exists."""
     ref.check_linear_attn(q, B, T, Hq, Hkv, log2_gamma)
+    if cum is not None:
+        if _gpu(q):
+            gq, gk = ext().linear_attn_bwd(q, k, v, do, dq, dk, dv, log2_gamma, B, T, Hq, Hkv, cum)
+            return gq, gk
+        return ref.linear_attn_gated_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, cum)
     if _gpu(q):
         ext().linear_attn_bwd(q, k, v, do, dq, dk, dv, log2_gamma, B, T, Hq, Hkv)
     else:

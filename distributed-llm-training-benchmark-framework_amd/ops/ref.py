@@ -734,6 +734,109 @@ def linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, log2_gamma):
     dv.copy_(dvh.permute(0, 2, 3, 1, 4).reshape(B * T, Hkv * D).to(dv.dtype))
 
 
+# ---- data-dependent decay gates (csrc/linear_attn_gate.hip; the contract of its kernels)
+#   z[t,g] = xn[t] . Wg[g] (fp32),  l = log2 sigmoid(z + b_g) = min(u, 0) - log2(1 + exp2(-|u|)), u = (z + b_g) log2(e)
+#   o[i] = scale sum_{j <= i} exp2(L[i] - L[j]) (q[i] . k[j]) v[j],  L = the running sum of l along a row
+# with b_g = ln(gamma_g / (1 - gamma_g)) of the fixed schedule, so Wg = 0 gives the decays gamma_g; no row normaliser.
+# The kernels read ``cum`` [B*T, Hkv] fp32, the inclusive prefix sum of l inside each chunk, and form every decay as
+# exp2 of a difference of two of a chunk's values.  The rounding points are those of the fixed-decay form.
+def linear_attn_gate_bias(Hkv, device=None):
+    """fp32 [Hkv]: b_g = ln(gamma_g / (1 - gamma_g)) = -ln(expm1(-ln gamma_g)) of :func:`linear_attn_log2_gamma`'s decays,
+    so sigmoid(b_g) = gamma_g."""
+    lg = linear_attn_log2_gamma(Hkv).double() * math.log(2.0)
+    return (-torch.log(torch.expm1(-lg))).float().to(device)
+
+
+def _gate_log2_sigmoid(z, bias):
+    u = (z + bias) * math.log2(math.e)
+    return torch.minimum(u, torch.zeros_like(u)) - torch.log2(1.0 + torch.exp2(-u.abs()))
+
+
+def linear_attn_gate_fwd(xn, wg, bias, B, T):
+    """xn [B*T, d], wg [Hkv, d] (16-bit, or fp64), bias fp32 [Hkv] -> (z, cum), both [B*T, Hkv] in fp32 (fp64)."""
+    ct = torch.float64 if xn.dtype == torch.float64 else torch.float32
+    z = xn.to(ct) @ wg.to(ct).t()
+    l = _gate_log2_sigmoid(z, bias.to(ct))
+    cum = l.view(B, T // LINEAR_ATTN_CHUNK, LINEAR_ATTN_CHUNK, -1).cumsum(2).reshape(B * T, -1)
+    return z, cum
+
+
+def linear_attn_gate_bwd(gq, gk, z, bias, wg, dxn, B, T):
+    """dz = dl (1 - a) with dl the suffix sum along each row of ``sum_{h in g} gq - gk`` and a = sigmoid(z + bias)
+    rebuilt from z (``z`` None: dl itself); with ``dxn``: dxn = round(float(dxn) + dz Wg) in place."""
+    Hkv = gk.shape[1]
+    dL = gq.view(B, T, Hkv, -1).sum(-1) - gk.view(B, T, Hkv)
+    dz = dL.flip(1).cumsum(1).flip(1).reshape(B * T, Hkv)
+    if z is not None:
+        dz = dz * (1.0 - 1.0 / (1.0 + torch.exp2(-(z + bias.to(z.dtype)) * math.log2(math.e))))
+    if dxn is not None:
+        dxn.copy_((dxn.to(dz.dtype) + dz @ wg.to(dz.dtype)).to(dxn.dtype))
+    return dz
+
+
+def _lag_tables(cum, B, nc, Hkv, C, scale):
+    """The decay tables of the gated form from ``cum``: [B, Hkv, nc, C(, C)] each, and the chunks' total decays."""
+    lam = cum.view(B, nc, C, Hkv).permute(0, 3, 1, 2)                        # [B, Hkv, nc, C]
+    a = torch.arange(C, device=cum.device)
+    diff = lam[..., :, None] - lam[..., None, :]                             # Lambda_a - Lambda_b
+    M = torch.where(a[:, None] >= a[None, :], torch.exp2(diff.clamp(max=0)), torch.zeros((), device=cum.device, dtype=cum.dtype))
+    return {"M": M, "din": torch.exp2(lam), "dout": torch.exp2(lam[..., -1:] - lam),
+            "gC": torch.exp2(lam[..., -1]), "scale": scale}
+
+
+def _lag_scan(local, gC, rd, reverse):
+    """:func:`_la_scan` with chunk c's own decay ``gC[..., c]`` at step c."""
+    nc = local.shape[2]
+    s = torch.zeros_like(local[:, :, 0])
+    out = torch.empty_like(local)
+    for c in (range(nc - 1, -1, -1) if reverse else range(nc)):
+        out[:, :, c] = rd(s)
+        s = gC[:, :, c, None, None] * s + local[:, :, c]
+    return out
+
+
+def _lag_setup(q, k, v, B, T, Hq, Hkv, cum):
+    l2g = torch.full((Hkv,), -1.0)                                           # unused: the shapes' checks only
+    D, C, G, nc, rd, _, qh, kh, vh = _la_setup(q, k, v, B, T, Hq, Hkv, l2g)
+    t = _lag_tables(cum.to(qh.dtype), B, nc, Hkv, C, 1.0 / math.sqrt(D))
+    return D, C, G, nc, rd, t, qh, kh, vh
+
+
+def linear_attn_gated_fwd(q, k, v, B, T, Hq, Hkv, cum):
+    """:func:`linear_attn_fwd` with the decays of ``cum`` (fp32 [B*T, Hkv]) and without the row normaliser."""
+    D, C, G, nc, rd, t, qh, kh, vh = _lag_setup(q, k, v, B, T, Hq, Hkv, cum)
+    local = torch.einsum("bgcnd,bgcne->bgcde", kh, rd(vh * t["dout"][..., None]))
+    S = _lag_scan(local, t["gC"], rd, False)
+    P = rd(torch.einsum("bghcad,bgcnd->bghcan", qh, kh) * t["M"][:, :, None])
+    o = torch.einsum("bghcan,bgcne->bghcae", P, vh) \
+        + t["din"][:, :, None, :, :, None] * torch.einsum("bghcad,bgcde->bghcae", qh, S)
+    return (o * t["scale"]).permute(0, 3, 4, 1, 2, 5).reshape(B * T, Hq * D).to(q.dtype)
+
+
+def linear_attn_gated_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, cum):
+    """:func:`linear_attn_bwd` for the gated form; returns (gq [B*T, Hq], gk [B*T, Hkv]) = (dq . q, dk . k) per row,
+    taken from the unrounded dq and dk."""
+    D, C, G, nc, rd, t, qh, kh, vh = _lag_setup(q, k, v, B, T, Hq, Hkv, cum)
+    doh = do.to(qh.dtype).reshape(B, nc, C, Hkv, G, D).permute(0, 3, 4, 1, 2, 5)
+    M, sc = t["M"][:, :, None], t["scale"]
+    din, dout = t["din"][:, :, None, :, :, None], t["dout"][..., None]
+    S = _lag_scan(torch.einsum("bgcnd,bgcne->bgcde", kh, rd(vh * dout)), t["gC"], rd, False)
+    dP = torch.einsum("bghcae,bgcne->bghcan", doh, vh)
+    dqh = sc * (torch.einsum("bghcan,bgcnd->bghcad", rd(dP * M), kh)
+                + din * torch.einsum("bghcae,bgcde->bghcad", doh, S))
+    dS = _lag_scan(torch.einsum("bghcad,bghcae->bgcde", qh, rd(doh * (sc * din))), t["gC"], rd, True)
+    f = M * sc
+    Sm = rd(torch.einsum("bghcad,bgcnd->bghcan", qh, kh) * f)
+    dkh = torch.einsum("bghcan,bghcad->bgcnd", rd(dP * f), qh) + dout * torch.einsum("bgcde,bgcne->bgcnd", dS, vh)
+    dvh = torch.einsum("bghcan,bghcae->bgcne", Sm, doh) + dout * torch.einsum("bgcnd,bgcde->bgcne", kh, dS)
+    dq.copy_(dqh.permute(0, 3, 4, 1, 2, 5).reshape(B * T, Hq * D).to(dq.dtype))
+    dk.copy_(dkh.permute(0, 2, 3, 1, 4).reshape(B * T, Hkv * D).to(dk.dtype))
+    dv.copy_(dvh.permute(0, 2, 3, 1, 4).reshape(B * T, Hkv * D).to(dv.dtype))
+    gq = (dqh * qh).sum(-1).permute(0, 3, 4, 1, 2).reshape(B * T, Hq)
+    gk = (dkh * kh).sum(-1).permute(0, 2, 3, 1).reshape(B * T, Hkv)
+    return gq, gk
+
+
 # ------------------------------------------------------------------------------ mixture of experts
 # Top-k routing with a fixed capacity (csrc/moe.hip).  N token rows, E experts, K choices per token, C slots per
 # expert.  Index tensors are int32: expert / slot [N, K], src / src_k [E * C], counts [E]; slot -1 = dropped

@@ -31,12 +31,13 @@ TILE = 64
 def muon_matrices(model) -> List[tuple]:
     """(unit, index, name, shape) of the parameters Muon updates: every 2-D parameter of a transformer block whose
     two dimensions are multiples of 64, as the model stores it (fused QKV and gate/up are one matrix each), except
-    the MoE router and the expert weights.  Embeddings, the LM head, norms, biases, sinks stay on AdamW."""
+    the MoE router, linear attention's decay gate and the expert weights.  Embeddings, the LM head, norms, biases,
+    sinks stay on AdamW."""
     out = []
     for u in model.unit_blocks:
         for i, (name, p) in enumerate(zip(u.names, u.params)):
             if p.dim() == 2 and p.shape[0] % TILE == 0 and p.shape[1] % TILE == 0 \
-                    and ".router." not in name and ".experts." not in name:
+                    and ".router." not in name and ".decay_gate." not in name and ".experts." not in name:
                 out.append((u, i, name, tuple(p.shape)))
     return out
 

@@ -87,6 +87,67 @@ def run(T, iters, rounds, ring_mib, emit, B=1, Hq=32, Hkv=8, D=128):
     return (med["linear fwd"] + med["linear bwd"]) / (med["softmax fwd"] + med["softmax bwd"])
 
 
+def run_gate(T, iters, rounds, ring_mib, emit, B=1, Hq=32, Hkv=8, D=128, d=4096):
+    """One layer's mixer under ``--linear-attn-gate`` (gate_fwd, the gated forward and backward, gate_bwd with its
+    in-place dxn term, the gate's weight gradient) against the fixed-decay forward + backward, same operands."""
+    dev = "cuda"
+    qd, kd = Hq * D, Hkv * D
+    per_set = B * T * (qd + 2 * kd + qd + 2 * d) * 2
+    n = max(2, -(-ring_mib * 2 ** 20 // per_set))
+    g = torch.Generator(device=dev).manual_seed(0)
+    l2g, bias = F_.linear_attn_log2_gamma(Hkv, dev), F_.linear_attn_gate_bias(Hkv, dev)
+    wg = (0.02 * torch.randn(Hkv, d, device=dev, generator=g)).bfloat16()
+    dwg = torch.empty_like(wg)
+    sets = []
+    for _ in range(n):
+        qkv = torch.randn(B * T, qd + 2 * kd, device=dev, dtype=torch.bfloat16, generator=g)
+        do = torch.randn(B * T, qd, device=dev, dtype=torch.bfloat16, generator=g)
+        xn = torch.randn(B * T, d, device=dev, dtype=torch.bfloat16, generator=g)
+        sets.append((qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], do, xn, torch.zeros_like(xn)))
+    o = torch.empty(B * T, qd, device=dev, dtype=torch.bfloat16)
+    dqkv = torch.empty(B * T, qd + 2 * kd, device=dev, dtype=torch.bfloat16)
+    dq, dk, dv = dqkv[:, :qd], dqkv[:, qd:qd + kd], dqkv[:, qd + kd:]
+    z0, cum0 = F_.linear_attn_gate_fwd(sets[0][4], wg, bias, B, T)
+    gq0, gk0 = torch.randn(B * T, Hq, device=dev, generator=g), torch.randn(B * T, Hkv, device=dev, generator=g)
+
+    def fixed(i):
+        q, k, v, do = sets[i % n][:4]
+        F_.linear_attn_fwd(q, k, v, B, T, Hq, Hkv, l2g, o_out=o)
+        F_.linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, l2g)
+
+    def gated(i):
+        q, k, v, do, xn, dxn = sets[i % n]
+        z, cum = F_.linear_attn_gate_fwd(xn, wg, bias, B, T)
+        F_.linear_attn_fwd(q, k, v, B, T, Hq, Hkv, l2g, o_out=o, cum=cum)
+        gq, gk = F_.linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, l2g, cum=cum)
+        dz = F_.linear_attn_gate_bwd(gq, gk, z, bias, wg, dxn, B, T)
+        F_.moe_router_wgrad(dz, xn, dwg, False, dense=True)
+
+    def gate_fwd(i):
+        F_.linear_attn_gate_fwd(sets[i % n][4], wg, bias, B, T)
+
+    def gate_bwd(i):
+        F_.linear_attn_gate_bwd(gq0, gk0, z0, bias, wg, sets[i % n][5], B, T)
+
+    fns = {"fixed fwd+bwd": fixed, "gated fwd+bwd": gated, "gate_fwd": gate_fwd, "gate_bwd": gate_bwd}
+    times = {key: [] for key in fns}
+    for r in range(rounds + 1):                 # round 0 warms up
+        for key, fn in fns.items():
+            us = timeit(fn, iters)
+            if r:
+                times[key].append(us)
+    med = {key: sorted(t)[len(t) // 2] for key, t in times.items()}
+    emit(f"T {T:6d}  ring {n} sets of {per_set / 2 ** 20:.0f} MiB")
+    for key in fns:
+        emit(f"    {key:14s} {med[key]:10.1f} us  ({min(times[key]):.1f} .. {max(times[key]):.1f})")
+    lo, hi = min(times["fixed fwd+bwd"]) / med["fixed fwd+bwd"], max(times["fixed fwd+bwd"]) / med["fixed fwd+bwd"]
+    ratio = med["gated fwd+bwd"] / med["fixed fwd+bwd"]
+    emit(f"    gated / fixed: {ratio:.3f}; the fixed call's own spread is {lo:.3f} .. {hi:.3f}: "
+         f"{'outside' if ratio > hi or ratio < lo else 'inside'} it")
+    del sets
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seq-lens", default="4096,16384,32768")
@@ -94,12 +155,27 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--ring-mib", type=int, default=320)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--gate", action="store_true",
+                    help="measure one layer's mixer under --linear-attn-gate against the fixed-decay calls instead")
     a = ap.parse_args()
     lines = []
 
     def emit(s):
         print(s, flush=True)
         lines.append(s)
+    if a.gate:
+        emit("# scripts/bench_linear_attn.py --gate: gated linear attention (csrc/linear_attn_gate.hip: gate_fwd, gated fwd,")
+        emit("# gated bwd, gate_bwd with the in-place dxn term, the gate's weight gradient) against the fixed-decay fwd + bwd,")
+        emit(f"# M7B head shape (B 1, Hq 32, Hkv 8, D 128, n_embd 4096, bf16), {torch.cuda.get_device_name(0)}; medians of "
+             f"{a.rounds}")
+        emit(f"# interleaved rounds of {a.iters} calls (min .. max), operand rings of more than {a.ring_mib} MiB.")
+        for T in (int(t) for t in a.seq_lens.split(",")):
+            run_gate(T, a.iters, a.rounds, a.ring_mib, emit)
+        emit("# not measured: the end-to-end step under --linear-attn-gate, loss curves, several GPUs")
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     emit("# scripts/bench_linear_attn.py: fixed-decay linear attention against full-causal softmax attention, M7B head")
     emit(f"# shape (B 1, Hq 32, Hkv 8, D 128, bf16), {torch.cuda.get_device_name(0)}; medians of {a.rounds} interleaved "
          f"rounds of {a.iters} calls")
