@@ -229,6 +229,31 @@ void dltb_linear_attn_gated_bwd(const void* q, const void* k, const void* v, con
                                 long ks, long vs, long dos, long dqs, long dks, long dvs, int B, int T, int Hq, int Hkv,
                                 int D, float scale, hipStream_t st);
 
+// the dxn step of gate_bwd alone, for a gate weight of `rows` rows: dxn [N, d] += dz [N, rows] wg [rows, d] in place
+void dltb_linear_attn_gate_dxn(void* dxn, const void* wg, const float* dz, long N, int d, int rows, hipStream_t st);
+
+// ---- linear_attn_chgate.hip: per-channel decay gates (the GLA form), o[i] = scale sum_{j<=i} (sum_d q[i,d] k[j,d]
+// exp2(L[i,d] - L[j,d])) v[j].  gate_fwd: xn [B T, d], w1 [R, d], w2 [kvd, R] 16-bit contiguous, bias fp32 [kvd / D] ->
+// z1 fp32 [B T, R] and cum fp32 [B T, kvd] (the prefix sum inside each chunk of l = log2 sigmoid(z1 w2^T + bias)).
+// chgate_fwd / _bwd: dltb_linear_attn_gated_fwd / _bwd with cum [B T, Hkv D]; the backward writes gq [B T, Hq D] =
+// dq * q and gk [B T, Hkv D] = dk * k per channel from its fp32 accumulators.  gate_bwd: dl (may be null) and dz
+// [B T, kvd] (suffix sum of sum_{h in g} gq - gk; dz = dl (1 - sigmoid)), dz1 [B T, R] = dz w2, and, when dw2 is not
+// null, dw2 [kvd, R] (+)= dz^T z1 through part (fp32 [dltb_linear_attn_chgate_slabs(B T), kvd, R]).
+bool dltb_linear_attn_chgate_supported(int T, int d, int R, int kvd);
+int dltb_linear_attn_chgate_slabs(long N);
+void dltb_linear_attn_chgate_gate_fwd(const void* xn, const void* w1, const void* w2, const float* bias, float* z1,
+                                      float* cum, int B, int T, int d, int R, int kvd, int D, hipStream_t st);
+void dltb_linear_attn_chgate_gate_bwd(const float* gq, const float* gk, const float* z1, const void* w2,
+                                      const float* bias, float* dl, float* dz, float* dz1, float* part, void* dw2,
+                                      int accumulate, int B, int T, int Hq, int Hkv, int D, int R, hipStream_t st);
+void dltb_linear_attn_chgate_fwd(const void* q, const void* k, const void* v, void* o, const float* cum, float* local,
+                                 void* state, long qs, long ks, long vs, long os, int B, int T, int Hq, int Hkv, int D,
+                                 float scale, hipStream_t st);
+void dltb_linear_attn_chgate_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk,
+                                 void* dv, const float* cum, float* gq, float* gk, float* local, void* state, long qs,
+                                 long ks, long vs, long dos, long dqs, long dks, long dvs, int B, int T, int Hq, int Hkv,
+                                 int D, float scale, hipStream_t st);
+
 // ---- batched column reductions (colreduce.hip)
 #ifndef DLTB_LAUNCHER_TYPES   // types once (launchers_f16.h repeats only the declarations)
 #define DLTB_LAUNCHER_TYPES

@@ -472,6 +472,12 @@ void dltb_linear_attn_gate_bwd(const float* gq, const float* gk, const float* z,
                      (const bf16_t*)wg, dz, (long)B * T, d, Hkv);
 }
 
+void dltb_linear_attn_gate_dxn(void* dxn, const void* wg, const float* dz, long N, int d, int rows, hipStream_t st) {
+  allow_dynamic_lds<lg_gate_dxn_kernel>(kGateLds);
+  hipLaunchKernelGGL(lg_gate_dxn_kernel, dim3((unsigned)((N + kC - 1) / kC)), dim3(256), (size_t)rows * d * 2, st,
+                     (bf16_t*)dxn, (const bf16_t*)wg, dz, N, d, rows);
+}
+
 void dltb_linear_attn_gated_fwd(const void* q, const void* k, const void* v, void* o, const float* cum, float* local,
                                 void* state, long qs, long ks, long vs, long os, int B, int T, int Hq, int Hkv, int D,
                                 float scale, hipStream_t st) {

@@ -131,6 +131,10 @@ def build_parser():
                         "lightning form, one decay 1 - 2^(-5 - 8 g / kv_heads) per KV head, a [head_dim, head_dim] "
                         "state, linear in the sequence length) in softmax attention's place; no parameter; not with "
                         "--context-parallel, --sliding-window, --doc-len, --attn-sinks or --attn-softcap; default: off")
+    p.add_argument("--linear-attn-gate-rank", type=int, default=0, metavar="R",
+                   help="with --linear-attn-gate: per-channel decays (the GLA / RWKV-6 form), one gate per token, KV "
+                        "head and key channel through a low-rank pair [R, n_embd] and [kv_heads * head_dim, R] (the "
+                        "second zero-initialised); R a multiple of 8 up to 64; default: 0, the scalar gate")
     p.add_argument("--linear-attn-gate", action="store_true",
                    help="with --linear-attn: data-dependent decays (the Mamba-2 / gated-RetNet form), per token and KV "
                         "head the scalar sigmoid(xn . Wg[g] + b_g) in the fixed decay's place and no row normaliser; one "
@@ -327,11 +331,15 @@ def check_fp8_linear(on, mcfg, tier, loss_scaling=False):
     mcfg.validate()
 
 
-def check_linear_attn(on, mcfg, tier, cp=1, gate=False):
+def check_linear_attn(on, mcfg, tier, cp=1, gate=False, rank=0):
     """ValueError when ``--linear-attn`` is set for a tier or a job it does not cover (``mcfg`` carries the job's other
     attention switches by now), or ``--linear-attn-gate`` (``gate``) without it; sets them on ``mcfg``."""
     if gate and not on:
         raise ValueError("--linear-attn-gate needs --linear-attn: it gates the decays of the linear-attention mixer")
+    if rank and not gate:
+        raise ValueError("--linear-attn-gate-rank needs --linear-attn-gate: it makes that gate per-channel")
+    if rank and not mcfg.causal:
+        raise ValueError(f"--linear-attn-gate-rank needs a causal tier (M7B, M7B_narrow, mtiny), got tier {tier}")
     if not on:
         return
     if not mcfg.causal:
@@ -342,6 +350,7 @@ def check_linear_attn(on, mcfg, tier, cp=1, gate=False):
                          "passed between ranks")
     mcfg.linear_attn = True
     mcfg.linear_attn_gate = bool(gate)
+    mcfg.linear_attn_gate_rank = rank
     mcfg.validate()
 
 
@@ -523,7 +532,7 @@ def train(args):
         check_final_softcap(getattr(args, "final_softcap", 0.0), mcfg, args.tier)
         check_lm_z_loss(getattr(args, "lm_z_loss_coef", 0.0), mcfg, args.tier)
         check_linear_attn(bool(getattr(args, "linear_attn", False)), mcfg, args.tier, cp_n,
-                          bool(getattr(args, "linear_attn_gate", False)))
+                          bool(getattr(args, "linear_attn_gate", False)), getattr(args, "linear_attn_gate_rank", 0))
         with torch.device(device):      # init directly on the GPU (no fp32 host copy of a 7B model)
             model = build_model(mcfg)
         if recompute != "off":          # a layout like cp, not a model property: the harness sets it on the model
@@ -739,6 +748,7 @@ def train(args):
             "fp8_linear": bool(mcfg.fp8_linear),
             "linear_attn": bool(mcfg.linear_attn),
             "linear_attn_gate": bool(mcfg.linear_attn_gate),
+            "linear_attn_gate_rank": int(mcfg.linear_attn_gate_rank),
             "attn_softcap": float(mcfg.attn_softcap),
             "final_softcap": float(mcfg.final_softcap),
             "lm_z_loss_coef": float(mcfg.lm_z_loss_coef),
@@ -855,7 +865,8 @@ def main(argv=None):
             cfg0.sliding_window = args.sliding_window
             cfg0.doc_eos_id = None if args.doc_len is None else cfg0.vocab_size - 1
             cfg0.attn_sinks, cfg0.attn_softcap = bool(args.attn_sinks), float(args.attn_softcap)
-        check_linear_attn(args.linear_attn, cfg0, args.tier, args.context_parallel, args.linear_attn_gate)
+        check_linear_attn(args.linear_attn, cfg0, args.tier, args.context_parallel, args.linear_attn_gate,
+                          args.linear_attn_gate_rank)
     except ValueError as e:
         parser.error(str(e))
     if args.strategy in ("zero2", "zero3") and not args.deepspeed_config:

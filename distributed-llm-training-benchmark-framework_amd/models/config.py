@@ -99,6 +99,11 @@ class ModelConfig:
     # initialised parameter self_attn.decay_gate.weight [kv_heads, n_embd] (the last of a layer) starts from the RetNet
     # decays (csrc/linear_attn_gate.hip).  Needs linear_attn and n_embd % 8 == 0.
     linear_attn_gate: bool = False
+    # per-channel decay gates (the GLA / RWKV-6 form): rank R > 0 makes the gate one decay per token, KV head and key
+    # channel through a low-rank pair, self_attn.decay_gate.weight [R, n_embd] and self_attn.decay_gate.up.weight
+    # [kv_heads * head_dim, R] (zeros, the layer's last parameter: training starts from the RetNet decays)
+    # (csrc/linear_attn_chgate.hip).  0: the scalar gate, or none.  Needs linear_attn_gate; R a multiple of 8 up to 64.
+    linear_attn_gate_rank: int = 0
 
     def __post_init__(self):
         self.validate()
@@ -180,8 +185,18 @@ class ModelConfig:
         if self.linear_attn_gate and not self.linear_attn:
             raise ValueError("--linear-attn-gate (linear_attn_gate, data-dependent decay gates) needs --linear-attn "
                              "(linear_attn)")
-        if self.linear_attn_gate and (self.n_embd % 8 or self.kv_heads > 64
-                                      or self.kv_heads * (2 * self.n_embd + 256) > 160 * 1024):
+        R = self.linear_attn_gate_rank
+        if isinstance(R, bool) or not isinstance(R, int) or R < 0:
+            raise ValueError(f"--linear-attn-gate-rank (linear_attn_gate_rank) must be an int >= 0, got {R!r}")
+        if R and not self.linear_attn_gate:
+            raise ValueError("--linear-attn-gate-rank (linear_attn_gate_rank, per-channel decay gates) needs "
+                             "--linear-attn-gate (linear_attn_gate)")
+        if R and (R % 8 or R > 64 or self.n_embd % 8 or R * (2 * self.n_embd + 256) > 160 * 1024):
+            raise ValueError("--linear-attn-gate-rank (linear_attn_gate_rank) needs a multiple of 8 up to 64, n_embd % 8 "
+                             "== 0 and rank * (2 * n_embd + 256) <= 160 KiB (the gate weight is staged in LDS), got rank "
+                             f"{R}, n_embd {self.n_embd}")
+        if self.linear_attn_gate and not R and (self.n_embd % 8 or self.kv_heads > 64
+                                                or self.kv_heads * (2 * self.n_embd + 256) > 160 * 1024):
             raise ValueError("--linear-attn-gate (linear_attn_gate) needs n_embd % 8 == 0, kv_heads <= 64 and "
                              "kv_heads * (2 * n_embd + 256) <= 160 KiB (the gate weight is staged in LDS), got n_embd "
                              f"{self.n_embd}, kv_heads {self.kv_heads}")
@@ -258,7 +273,9 @@ class ModelConfig:
             per_block += 2 * d
         if self.attn_sinks:      # one sink logit per query head
             per_block += self.n_head
-        if self.linear_attn_gate:    # the decay gate's weight
+        if self.linear_attn_gate_rank:   # the per-channel gate's low-rank pair
+            per_block += self.linear_attn_gate_rank * (d + kvd)
+        elif self.linear_attn_gate:  # the decay gate's weight
             per_block += self.kv_heads * d
         head = 0 if self.tie_embeddings else V * d
         return V * d + L * per_block + d + head
@@ -279,7 +296,8 @@ class ModelConfig:
         (2 * C/2 * head_dim each per query head, C = ``ops.ref.LINEAR_ATTN_CHUNK``), the query by the state (2 * head_dim^2 per query head) and
         builds the state (2 * head_dim^2 per KV head); times 3 for forward + backward,
         ``attn = 6 * L * (d * (C + head_dim) + kv_dim * head_dim)``.  The states the backward rebuilds are not
-        counted, and no T x T product is.  ``linear_attn_gate`` adds the gate's projection, ``6 * L * n_embd * kv_heads``."""
+        counted, and no T x T product is.  ``linear_attn_gate`` adds the gate's projection, ``6 * L * n_embd * kv_heads``, or with
+        ``linear_attn_gate_rank`` R its low-rank pair, ``6 * L * R * (n_embd + kv_dim)``."""
         d, L = self.n_embd, self.n_layer
         if self.arch == "tinygpt":
             n_mat = L * (4 * d * d + 2 * d * self.ffn_dim) + self.vocab_size * d
@@ -298,7 +316,9 @@ class ModelConfig:
         if self.linear_attn:
             from ..ops.ref import LINEAR_ATTN_CHUNK as C      # the kernels' chunk (csrc/linear_attn.hip kC)
             attn = 6.0 * L * (d * (C + self.head_dim) + self.kv_heads * self.head_dim * self.head_dim)
-            if self.linear_attn_gate:
+            if self.linear_attn_gate_rank:
+                attn += 6.0 * L * self.linear_attn_gate_rank * (d + self.kv_heads * self.head_dim)
+            elif self.linear_attn_gate:
                 attn += 6.0 * L * d * self.kv_heads
         return 6.0 * n_mat + attn
 

@@ -60,6 +60,11 @@ product's data gradient exists, ``linear_attn_gate_bwd`` forms dz from them and 
 place, and the weight gradient goes through the MoE router's dense kernel.  Engines treat the weight like the
 router's: AdamW updates it (Muon leaves it to its inner AdamW) and ``fp8_linear`` leaves its product 16-bit.
 
+With ``cfg.linear_attn_gate_rank`` R the gate is per key channel (csrc/linear_attn_chgate.hip): the gate weight is
+[R, n_embd] and ``self_attn.decay_gate.up.weight`` [kv_heads * head_dim, R] follows it as the layer's last parameter
+(zeros at the start).  The same calls take ``up=``: kept are z1 [B*T, R] and cum [B*T, kv_heads * head_dim], the mixer's
+backward returns the per-channel products, and ``linear_attn_gate_bwd`` also forms the up-projection's gradient.
+
 With ``cfg.sandwich_norm`` every sublayer's output goes through its own RMSNorm before it joins the residual stream,
 ``x1 = x + RMSNorm(a; self_attn.out_norm)`` and ``x2 = x1 + RMSNorm(m; mlp.out_norm)`` (m: the dense FFN's output or the
 MoE combine), on top of the two pre-norms.  The two [n_embd] weights sit in the layer's parameter list after the
@@ -88,7 +93,7 @@ class _RMSNorm(nn.Module):
 
 
 class _Attn(nn.Module):
-    def __init__(self, d, kvd, qk_norm_dim=None, n_sinks=None, n_gates=None):
+    def __init__(self, d, kvd, qk_norm_dim=None, n_sinks=None, n_gates=None, gate_rank=0):
         super().__init__()
         self.qkv_proj = nn.Linear(d, d + 2 * kvd, bias=False)
         self.o_proj = nn.Linear(d, d, bias=False)
@@ -98,7 +103,9 @@ class _Attn(nn.Module):
         if n_sinks:             # attention sinks: one raw logit per query head
             self.sinks = nn.Parameter(torch.zeros(n_sinks))
         if n_gates:             # linear attention's decay gate: one row per KV head, zeros (MistralLM.__init__)
-            self.decay_gate = nn.Linear(d, n_gates, bias=False)
+            self.decay_gate = nn.Linear(d, gate_rank or n_gates, bias=False)
+            if gate_rank:       # per-channel gates: the low-rank pair's up-projection, zeros (MistralLM.__init__)
+                self.decay_gate.up = nn.Linear(gate_rank, kvd, bias=False)
 
 
 class _MLP(nn.Module):
@@ -124,7 +131,8 @@ class MistralLayer(nn.Module):
         self.input_layernorm = _RMSNorm(d)
         self.self_attn = _Attn(d, cfg.kv_heads * cfg.head_dim, cfg.head_dim if cfg.qk_norm else None,
                                cfg.n_head if cfg.attn_sinks else None,
-                               cfg.kv_heads if cfg.linear_attn_gate else None)
+                               cfg.kv_heads if cfg.linear_attn_gate else None, cfg.linear_attn_gate_rank)
+        self.linear_attn_gate_rank = cfg.linear_attn_gate_rank
         self.qk_norm = cfg.qk_norm
         self.attn_sinks = cfg.attn_sinks
         self.linear_attn_gate = cfg.linear_attn_gate
@@ -150,6 +158,8 @@ class MistralLayer(nn.Module):
             tail = tail + [("self_attn.sinks", self.self_attn.sinks)]
         if self.linear_attn_gate:
             tail = tail + [("self_attn.decay_gate.weight", self.self_attn.decay_gate.weight)]
+        if self.linear_attn_gate_rank:
+            tail = tail + [("self_attn.decay_gate.up.weight", self.self_attn.decay_gate.up.weight)]
         head = [("input_layernorm.weight", self.input_layernorm.weight),
                 ("self_attn.qkv_proj.weight", self.self_attn.qkv_proj.weight),
                 ("self_attn.o_proj.weight", self.self_attn.o_proj.weight),
@@ -189,7 +199,7 @@ def _n_block_weights(cfg, ws):
     """How many of a layer's parameters ``ws`` come before its tail -- the QK-norm pair, then the sandwich norms'
     pair, then the sinks or the decay gate -- that is the norms, projections and the FFN."""
     return len(ws) - (2 if cfg.qk_norm else 0) - (2 if cfg.sandwich_norm else 0) \
-        - (1 if cfg.attn_sinks or cfg.linear_attn_gate else 0)
+        - (1 if cfg.attn_sinks or cfg.linear_attn_gate else 0) - (1 if cfg.linear_attn_gate_rank else 0)
 
 
 def _attn_tail(cfg, ws):
@@ -361,16 +371,27 @@ def _linear_attn_bwd(model, qkv, do, dqkv, B, T, Hq, Hkv, D, qkn, raw, sq, sk, r
     return g
 
 
-def _gate_fwd(model, h1, wg, B, T):
-    """(z, cum) of the decay gate on the pre-attention norm output ``h1``; both are kept in every recompute mode."""
-    return F_.linear_attn_gate_fwd(h1, wg, model.linear_attn_gate_bias(h1.device), B, T)
+def _gate_weights(cfg, ws):
+    """(wg, up) of a layer's parameters ``ws``: the gate weight and, under ``cfg.linear_attn_gate_rank``, the
+    up-projection after it (the layer's last parameter), else None."""
+    return (ws[-2], ws[-1]) if cfg.linear_attn_gate_rank else (ws[-1], None)
 
 
-def _gate_bwd(model, g, gate, wg, h1, dh1, slot, B, T):
+def _gate_fwd(model, h1, wg, B, T, up=None):
+    """(z, cum) of the decay gate on the pre-attention norm output ``h1`` (``up``: (z1, cum) of the per-channel gate);
+    both are kept in every recompute mode."""
+    return F_.linear_attn_gate_fwd(h1, wg, model.linear_attn_gate_bias(h1.device), B, T, up=up)
+
+
+def _gate_bwd(model, g, gate, wg, h1, dh1, slot, B, T, up=None, up_slot=None):
     """The decay gate's backward, after the qkv product's data gradient ``dh1`` exists: dz from the row dots ``g`` and
     the kept z, its rank-kv_heads term added into ``dh1`` in place, and dWg = dz^T h1 into the gate's gradient slot
     (the MoE router's dense weight-gradient kernel: fp32 [N, kv_heads] times 16-bit rows, fixed-order partials)."""
-    dz = F_.linear_attn_gate_bwd(g[0], g[1], gate[0], model.linear_attn_gate_bias(h1.device), wg, dh1, B, T)
+    if up is not None:      # per-channel gates: dz1 = dz up in dz's place, and the up-projection's gradient dz^T z1
+        dz = F_.linear_attn_gate_bwd(g[0], g[1], gate[0], model.linear_attn_gate_bias(h1.device), wg, dh1, B, T, up=up,
+                                     dup=up_slot[0], accumulate=up_slot[1])[0]
+    else:
+        dz = F_.linear_attn_gate_bwd(g[0], g[1], gate[0], model.linear_attn_gate_bias(h1.device), wg, dh1, B, T)
     F_.moe_router_wgrad(dz, h1, slot[0], slot[1], dense=True)
 
 
@@ -399,7 +420,8 @@ class _LayerFn(torch.autograd.Function):
             raw = _rope_fwd(model, qkv, T, Hq, Hkv, D, qkn)
             lse = aux = None
             if cfg.linear_attn_gate:  # the decay gate (the layer's last parameter): z and cum, kept in every mode
-                ctx.gate = _gate_fwd(model, h1, ws[-1], B, T)
+                wg, up = _gate_weights(cfg, ws)
+                ctx.gate = _gate_fwd(model, h1, wg, B, T, up)
             o = F_.linear_attn_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, T, Hq, Hkv,
                                    model.linear_attn_decays(qkv.device), cum=ctx.gate and ctx.gate[1])
         elif model.cp is not None:    # context parallel: local queries against the group's gathered K | V
@@ -507,7 +529,8 @@ class _LayerFn(torch.autograd.Function):
         F_.linear_wgrad(dqkv, h1, s[1][0], None, s[1][1])
         dh1 = _lin_dgrad(model, unit, 1, dqkv, wqkv)
         if ctx.gate is not None:
-            _gate_bwd(model, gdots, ctx.gate, ws[-1], h1, dh1, s[-1], B, T)
+            wg, up = _gate_weights(cfg, ws)
+            _gate_bwd(model, gdots, ctx.gate, wg, h1, dh1, s[-1] if up is None else s[-2], B, T, up, s[-1])
             ctx.gate = None
         dx = F_.norm_bwd(dh1, x, w_in, None, rstd1, dx1, s[0][0], None, s[0][1], True, red=red)
         if shared is None:
@@ -766,7 +789,8 @@ def _layer_backward_recompute(ctx, dx2):
     dh1 = _lin_dgrad(model, unit, 1, dqkv, wqkv)
     del dqkv
     if ctx.gate is not None:      # the kept z and cum; h1 is the rebuilt one, the forward's bit for bit
-        _gate_bwd(model, gdots, ctx.gate, ws[-1], h1, dh1, s[-1], B, T)
+        wg, up = _gate_weights(cfg, ws)
+        _gate_bwd(model, gdots, ctx.gate, wg, h1, dh1, s[-1] if up is None else s[-2], B, T, up, s[-1])
         ctx.gate = None
     del h1
     dx = F_.norm_bwd(dh1, x, w_in, None, rstd1, dx1, s[0][0], None, s[0][1], True, red=red)
@@ -931,7 +955,8 @@ class MistralLM(nn.Module):
                 nn.init.normal_(mod.weight, mean=0.0, std=0.02)
         if cfg.linear_attn_gate:    # a zero gate weight: every layer starts from the fixed schedule's decays
             for layer in self.model.layers:
-                nn.init.zeros_(layer.self_attn.decay_gate.weight)
+                gate = layer.self_attn.decay_gate     # per-channel gates: the up-projection is the zero one
+                nn.init.zeros_(gate.up.weight if cfg.linear_attn_gate_rank else gate.weight)
         self.rt = EAGER
         self.drop_p = 0.0
         self._rope = {}

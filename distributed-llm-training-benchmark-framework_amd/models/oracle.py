@@ -147,8 +147,13 @@ class OracleMistral(nn.Module):
             if cfg.attn_sinks:      # one learned sink logit per query head
                 layer.self_attn.sinks = nn.Parameter(torch.zeros(cfg.n_head))
             if cfg.linear_attn_gate:    # linear attention's decay gate, one row per KV head, zeros
-                layer.self_attn.decay_gate = nn.Linear(d, cfg.kv_heads, bias=False)
-                nn.init.zeros_(layer.self_attn.decay_gate.weight)
+                R = cfg.linear_attn_gate_rank
+                layer.self_attn.decay_gate = nn.Linear(d, R or cfg.kv_heads, bias=False)
+                if R:               # per-channel gates: a low-rank pair, the up-projection zeros
+                    layer.self_attn.decay_gate.up = nn.Linear(R, kvd, bias=False)
+                    nn.init.zeros_(layer.self_attn.decay_gate.up.weight)
+                else:
+                    nn.init.zeros_(layer.self_attn.decay_gate.weight)
             layer.post_attention_layernorm = _RMSNorm(d, cfg.norm_eps)
             layer.mlp = nn.Module()
             if cfg.sandwich_norm:   # every sublayer's output through its own RMSNorm before the residual add
@@ -190,7 +195,22 @@ class OracleMistral(nn.Module):
             q, k = _rope(q, cos, sin), _rope(k, cos, sin)
             k = k.repeat_interleave(H // Hkv, 1)
             v = v.repeat_interleave(H // Hkv, 1)
-            if cfg.linear_attn_gate:
+            if cfg.linear_attn_gate_rank:
+                # the quadratic form with per-channel gates (GLA): one decay per token, KV head and key channel, the
+                # weight of a pair (i, j) is sum_d q[i,d] k[j,d] exp(L[i,d] - L[j,d]); one query head at a time
+                from ..ops import ref
+                gate = layer.self_attn.decay_gate
+                bias = ref.linear_attn_gate_bias(Hkv, idx.device).to(h.dtype).repeat_interleave(hd)
+                L = torch.nn.functional.logsigmoid(gate.up(gate(h)) + bias).cumsum(1)
+                L = L.view(B, T, Hkv, hd).transpose(1, 2).repeat_interleave(H // Hkv, 1)             # [B, H, T, hd]
+                causal = torch.tril(torch.ones(T, T, device=idx.device, dtype=q.dtype))
+                outs = []
+                for hh in range(H):
+                    E = torch.exp((L[:, hh, :, None, :] - L[:, hh, None, :, :]).clamp(max=0))       # [B, T, T, hd]
+                    s = torch.einsum("bid,bjd,bijd->bij", q[:, hh], k[:, hh], E) * (causal / math.sqrt(hd))
+                    outs.append(s @ v[:, hh])
+                o = torch.stack(outs, 1)
+            elif cfg.linear_attn_gate:
                 # the quadratic form of gated linear attention: per token and KV head the decay sigmoid(h . Wg[g] + b_g),
                 # the mask exp(L[i] - L[j]) with L the running sum of its logarithm along the row, no row normaliser
                 from ..ops import ref

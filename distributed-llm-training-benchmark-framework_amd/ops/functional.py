@@ -862,11 +862,25 @@ def linear_attn_gate_bias(Hkv, device=None):
     return ref.linear_attn_gate_bias(Hkv, device)
 
 
-def linear_attn_gate_fwd(xn, wg, bias, B, T):
+def linear_attn_gate_fwd(xn, wg, bias, B, T, up=None):
     """The decay gate of ``--linear-attn-gate`` (csrc/linear_attn_gate.hip; the contract is
     :func:`ref.linear_attn_gate_fwd`): ``z = xn Wg^T`` (16-bit operands, fp32) and ``cum``, the inclusive prefix sum
     inside each chunk of 64 rows of ``l = log2 sigmoid(z + bias)``; both fp32 [B*T, Hkv].  ``cum`` is what
-    :func:`linear_attn_fwd` / :func:`linear_attn_bwd` take as ``cum=``; ``z`` is kept for :func:`linear_attn_gate_bwd`."""
+    :func:`linear_attn_fwd` / :func:`linear_attn_bwd` take as ``cum=``; ``z`` is kept for :func:`linear_attn_gate_bwd`.
+
+    ``up`` [kv_heads * D, R] with ``wg`` [R, n_embd]: the per-channel gate of csrc/linear_attn_chgate.hip
+    (:func:`ref.linear_attn_chgate_gate_fwd`), ``z = (xn Wg^T) up^T``; returns (z1 fp32 [B*T, R], cum fp32 [B*T, kv_heads * D])."""
+    if up is not None:
+        R = wg.shape[0]
+        if T % ref.LINEAR_ATTN_CHUNK or xn.shape[1] % 8 or wg.shape[1] != xn.shape[1] or up.shape[1] != R \
+                or R % 8 or not 8 <= R <= 64 or up.shape[0] % (64 * bias.numel()):
+            raise ValueError(f"linear_attn_gate: the per-channel form needs T % {ref.LINEAR_ATTN_CHUNK} == 0, wg [R, n_embd] "
+                             f"with R a multiple of 8 up to 64 and up [kv_heads * D, R], got T {T}, xn {tuple(xn.shape)}, "
+                             f"wg {tuple(wg.shape)}, up {tuple(up.shape)}")
+        if _gpu(xn):
+            z1, cum = ext().linear_attn_chgate_gate_fwd(xn, wg, up, bias, B, T)
+            return z1, cum
+        return ref.linear_attn_chgate_gate_fwd(xn, wg, up, bias, B, T)
     if T % ref.LINEAR_ATTN_CHUNK or xn.shape[1] % 8 or wg.shape[1] != xn.shape[1] or bias.numel() != wg.shape[0]:
         raise ValueError(f"linear_attn_gate: needs T % {ref.LINEAR_ATTN_CHUNK} == 0, n_embd % 8 == 0, wg [kv_heads, "
                          f"n_embd] and bias [kv_heads], got T {T}, xn {tuple(xn.shape)}, wg {tuple(wg.shape)}")
@@ -876,12 +890,21 @@ def linear_attn_gate_fwd(xn, wg, bias, B, T):
     return ref.linear_attn_gate_fwd(xn, wg, bias, B, T)
 
 
-def linear_attn_gate_bwd(gq, gk, z, bias, wg, dxn, B, T):
+def linear_attn_gate_bwd(gq, gk, z, bias, wg, dxn, B, T, up=None, dup=None, accumulate=False):
     """The gate's backward from the two row dots :func:`linear_attn_bwd` returns under ``cum=``: ``dl`` is the suffix
     sum along each row of T tokens of ``sum_{h in g} gq - gk`` (one fixed order, no atomics), ``dz = dl (1 - a)`` with
     ``a = sigmoid(z + bias)`` rebuilt from z; returns dz fp32 [B*T, Hkv] (``z`` None: dl).  With ``dxn`` [B*T, n_embd],
     the data gradient of the qkv product, ``dxn = round(float(dxn) + dz Wg)`` in place.  The weight gradient is
-    ``moe_router_wgrad(dz, xn, ..., dense=True)``."""
+    ``moe_router_wgrad(dz, xn, ..., dense=True)``.
+
+    ``up``: the per-channel form; gq [B*T, Hq*D], gk [B*T, kv_heads*D] and ``z`` is z1.  Returns (dz1 fp32 [B*T, R] =
+    dz up, dz, dl); ``dxn`` += dz1 Wg in place; ``dup`` [kv_heads*D, R] (+)= dz^T z1 (a fixed-order two-stage sum).
+    Wg's gradient is ``moe_router_wgrad(dz1, xn, ..., dense=True)``."""
+    if up is not None:
+        if _gpu(gq):
+            dz1, dz, dl = ext().linear_attn_chgate_gate_bwd(gq, gk, z, bias, wg, up, dxn, dup, accumulate, B, T)
+            return dz1, dz, dl
+        return ref.linear_attn_chgate_gate_bwd(gq, gk, z, bias, wg, up, dxn, dup, accumulate, B, T)
     if _gpu(gq):
         return ext().linear_attn_gate_bwd(gq, gk, z, bias, wg, dxn, B, T)
     return ref.linear_attn_gate_bwd(gq, gk, z, bias, wg, dxn, B, T)
@@ -905,6 +928,8 @@ def linear_attn_fwd(q, k, v, B, T, Hq, Hkv, log2_gamma, o_out=None, cum=None):
         return _into(o_out, ref.linear_attn_fwd(q, k, v, B, T, Hq, Hkv, log2_gamma))
     if _gpu(q):
         return ext().linear_attn_fwd(q, k, v, log2_gamma, B, T, Hq, Hkv, o_out, cum)
+    if cum.shape[1] != Hkv:       # [B*T, Hkv*D]: per-channel decays (csrc/linear_attn_chgate.hip)
+        return _into(o_out, ref.linear_attn_chgated_fwd(q, k, v, B, T, Hq, Hkv, cum))
     return _into(o_out, ref.linear_attn_gated_fwd(q, k, v, B, T, Hq, Hkv, cum))
 
 
@@ -920,6 +945,8 @@ def linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, log2_gamma, cum=None
         if _gpu(q):
             gq, gk = ext().linear_attn_bwd(q, k, v, do, dq, dk, dv, log2_gamma, B, T, Hq, Hkv, cum)
             return gq, gk
+        if cum.shape[1] != Hkv:   # per-channel decays: gq [B*T, Hq*D], gk [B*T, Hkv*D]
+            return ref.linear_attn_chgated_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, cum)
         return ref.linear_attn_gated_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, cum)
     if _gpu(q):
         ext().linear_attn_bwd(q, k, v, do, dq, dk, dv, log2_gamma, B, T, Hq, Hkv)

@@ -837,6 +837,84 @@ def linear_attn_gated_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, cum):
     return gq, gk
 
 
+# ---- per-channel decay gates (csrc/linear_attn_chgate.hip; the GLA form)
+#   z1 = xn W1^T (fp32, W1 [R, n_embd]),  z[t,c] = sum_r z1[t,r] W2[c,r] (W2 [Hkv D, R]),  l = log2 sigmoid(z + b_g), c = g D + d
+#   o[i] = scale sum_{j <= i} (sum_d q[i,d] k[j,d] exp2(L[i,d] - L[j,d])) v[j],  L = the running sum of l along a row
+# ``cum`` is [B*T, Hkv*D]: the prefix sum of l inside each chunk.  Rounded once each: the decayed K (q) operand of a state
+# product, the running state, the decayed query of the state's term and a chunk's score tile.  The kernels also round
+# the two decayed operands of an off-diagonal 16-row sub-block; here every intra-chunk weight is formed in full
+# precision, so this path is at least as close to the definition.  The backward is autograd through this forward.
+def linear_attn_chgate_gate_fwd(xn, w1, w2, bias, B, T):
+    """xn [B*T, d], w1 [R, d], w2 [Hkv*D, R] (16-bit, or fp64), bias fp32 [Hkv] -> (z1 [B*T, R], cum [B*T, Hkv*D])."""
+    ct = torch.float64 if xn.dtype == torch.float64 else torch.float32
+    z1 = xn.to(ct) @ w1.to(ct).t()
+    z = z1 @ w2.to(ct).t()
+    l = _gate_log2_sigmoid(z, bias.to(ct).repeat_interleave(w2.shape[0] // bias.numel()))
+    cum = l.view(B, T // LINEAR_ATTN_CHUNK, LINEAR_ATTN_CHUNK, -1).cumsum(2).reshape(B * T, -1)
+    return z1, cum
+
+
+def linear_attn_chgate_gate_bwd(gq, gk, z1, bias, w1, w2, dxn, dw2, accumulate, B, T):
+    """(dz1, dz, dl): dl the suffix sum along each row of ``sum_{h in g} gq - gk`` per channel, dz = dl (1 - a) with a
+    rebuilt from z1 and w2, dz1 = dz W2; ``dxn`` += dz1 W1 in place (rounded once), ``dw2`` (+)= dz^T z1."""
+    kvd, Hkv = gk.shape[1], bias.numel()
+    D = kvd // Hkv
+    dL = gq.view(B, T, Hkv, -1, D).sum(3) - gk.view(B, T, Hkv, D)
+    dl = dL.flip(1).cumsum(1).flip(1).reshape(B * T, kvd)
+    w2f = w2.to(dl.dtype)
+    zb = z1 @ w2f.t() + bias.to(dl.dtype).repeat_interleave(D)
+    dz = dl * (1.0 - 1.0 / (1.0 + torch.exp2(-zb * math.log2(math.e))))
+    dz1 = dz @ w2f
+    if dxn is not None:
+        dxn.copy_((dxn.to(dz.dtype) + dz1 @ w1.to(dz.dtype)).to(dxn.dtype))
+    if dw2 is not None:
+        v = dz.t() @ z1
+        dw2.copy_((v + dw2.to(v.dtype)) if accumulate else v)
+    return dz1, dz, dl
+
+
+def _lac_fwd(q, k, v, B, T, Hq, Hkv, cum):
+    l2g = torch.full((Hkv,), -1.0)
+    D, C, G, nc, rd, _, qh, kh, vh = _la_setup(q, k, v, B, T, Hq, Hkv, l2g)
+    lam = cum.to(qh.dtype).view(B, nc, C, Hkv, D).permute(0, 3, 1, 2, 4)            # [B, Hkv, nc, C, D]
+    a = torch.arange(C, device=q.device)
+    kd = rd(kh * torch.exp2(lam[:, :, :, -1:, :] - lam))
+    local = torch.einsum("bgcnd,bgcne->bgcde", kd, vh)
+    gC = torch.exp2(lam[:, :, :, -1, :])                                             # [B, Hkv, nc, D]
+    s = torch.zeros_like(local[:, :, 0])
+    S = []
+    for c in range(nc):
+        S.append(rd(s))
+        s = gC[:, :, c, :, None] * s + local[:, :, c]
+    S = torch.stack(S, 2)
+    diff = (lam[:, :, :, :, None, :] - lam[:, :, :, None, :, :]).clamp(max=0)        # [B, Hkv, nc, C, C, D]
+    W = torch.exp2(diff) * (a[:, None] >= a[None, :]).to(diff.dtype)[:, :, None]
+    P = rd(torch.einsum("bghcad,bgcnd,bgcand->bghcan", qh, kh, W))
+    o = torch.einsum("bghcan,bgcne->bghcae", P, vh) \
+        + torch.einsum("bghcad,bgcde->bghcae", rd(qh * torch.exp2(lam)[:, :, None]), S)
+    return (o / math.sqrt(D)).permute(0, 3, 4, 1, 2, 5).reshape(B * T, Hq * D)
+
+
+def linear_attn_chgated_fwd(q, k, v, B, T, Hq, Hkv, cum):
+    """:func:`linear_attn_gated_fwd` with one decay per key channel: ``cum`` is fp32 [B*T, Hkv*D]."""
+    with torch.no_grad():
+        return _lac_fwd(q, k, v, B, T, Hq, Hkv, cum).to(q.dtype)
+
+
+def linear_attn_chgated_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, cum):
+    """:func:`linear_attn_gated_bwd` for the per-channel form; returns (gq [B*T, Hq*D], gk [B*T, Hkv*D]) = (dq * q,
+    dk * k) per channel, taken from the unrounded dq and dk."""
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    with torch.enable_grad():
+        qf, kf, vf = (t.detach().to(ct).requires_grad_() for t in (q, k, v))
+        o = _lac_fwd(qf, kf, vf, B, T, Hq, Hkv, cum.detach())
+        gqf, gkf, gvf = torch.autograd.grad(o, (qf, kf, vf), do.detach().to(ct))
+    dq.copy_(gqf.to(dq.dtype))
+    dk.copy_(gkf.to(dk.dtype))
+    dv.copy_(gvf.to(dv.dtype))
+    return gqf * qf.detach(), gkf * kf.detach()
+
+
 # ------------------------------------------------------------------------------ mixture of experts
 # Top-k routing with a fixed capacity (csrc/moe.hip).  N token rows, E experts, K choices per token, C slots per
 # expert.  Index tensors are int32: expert / slot [N, K], src / src_k [E * C], counts [E]; slot -1 = dropped

@@ -87,9 +87,11 @@ def run(T, iters, rounds, ring_mib, emit, B=1, Hq=32, Hkv=8, D=128):
     return (med["linear fwd"] + med["linear bwd"]) / (med["softmax fwd"] + med["softmax bwd"])
 
 
-def run_gate(T, iters, rounds, ring_mib, emit, B=1, Hq=32, Hkv=8, D=128, d=4096):
+def run_gate(T, iters, rounds, ring_mib, emit, B=1, Hq=32, Hkv=8, D=128, d=4096, rank=0):
     """One layer's mixer under ``--linear-attn-gate`` (gate_fwd, the gated forward and backward, gate_bwd with its
-    in-place dxn term, the gate's weight gradient) against the fixed-decay forward + backward, same operands."""
+    in-place dxn term, the gate's weight gradient) against the fixed-decay forward + backward, same operands.
+    ``rank``: the per-channel gate of that rank (csrc/linear_attn_chgate.hip) against the scalar-gated calls, with a
+    per-kernel breakdown of the per-channel mixer calls."""
     dev = "cuda"
     qd, kd = Hq * D, Hkv * D
     per_set = B * T * (qd + 2 * kd + qd + 2 * d) * 2
@@ -130,6 +132,44 @@ def run_gate(T, iters, rounds, ring_mib, emit, B=1, Hq=32, Hkv=8, D=128, d=4096)
         F_.linear_attn_gate_bwd(gq0, gk0, z0, bias, wg, sets[i % n][5], B, T)
 
     fns = {"fixed fwd+bwd": fixed, "gated fwd+bwd": gated, "gate_fwd": gate_fwd, "gate_bwd": gate_bwd}
+    base = "fixed fwd+bwd"
+    if rank:
+        w1 = (0.02 * torch.randn(rank, d, device=dev, generator=g)).bfloat16()
+        w2 = (0.02 * torch.randn(kd, rank, device=dev, generator=g)).bfloat16()
+        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+        z10, cumc = F_.linear_attn_gate_fwd(sets[0][4], w1, bias, B, T, up=w2)
+        gqc, gkc = torch.randn(B * T, qd, device=dev, generator=g), torch.randn(B * T, kd, device=dev, generator=g)
+
+        def chan(i):
+            q, k, v, do, xn, dxn = sets[i % n]
+            z1, cum = F_.linear_attn_gate_fwd(xn, w1, bias, B, T, up=w2)
+            F_.linear_attn_fwd(q, k, v, B, T, Hq, Hkv, l2g, o_out=o, cum=cum)
+            gq, gk = F_.linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, l2g, cum=cum)
+            dz1 = F_.linear_attn_gate_bwd(gq, gk, z1, bias, w1, dxn, B, T, up=w2, dup=dw2)[0]
+            F_.moe_router_wgrad(dz1, xn, dw1, False, dense=True)
+
+        def chan_fwd(i):
+            q, k, v = sets[i % n][:3]
+            F_.linear_attn_fwd(q, k, v, B, T, Hq, Hkv, l2g, o_out=o, cum=cumc)
+
+        def chan_bwd(i):
+            q, k, v, do = sets[i % n][:4]
+            F_.linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, l2g, cum=cumc)
+
+        def scalar_fwd(i):
+            q, k, v = sets[i % n][:3]
+            F_.linear_attn_fwd(q, k, v, B, T, Hq, Hkv, l2g, o_out=o, cum=cum0)
+
+        def scalar_bwd(i):
+            q, k, v, do = sets[i % n][:4]
+            F_.linear_attn_bwd(q, k, v, do, dq, dk, dv, B, T, Hq, Hkv, l2g, cum=cum0)
+
+        fns = {"gated fwd+bwd": gated, "chgate fwd+bwd": chan, "scalar mixer fwd": scalar_fwd, "chgate mixer fwd": chan_fwd,
+               "scalar mixer bwd": scalar_bwd, "chgate mixer bwd": chan_bwd,
+               "chgate gate_fwd": lambda i: F_.linear_attn_gate_fwd(sets[i % n][4], w1, bias, B, T, up=w2),
+               "chgate gate_bwd": lambda i: F_.linear_attn_gate_bwd(gqc, gkc, z10, bias, w1, sets[i % n][5], B, T, up=w2,
+                                                                     dup=dw2)}
+        base = "gated fwd+bwd"
     times = {key: [] for key in fns}
     for r in range(rounds + 1):                 # round 0 warms up
         for key, fn in fns.items():
@@ -139,10 +179,11 @@ def run_gate(T, iters, rounds, ring_mib, emit, B=1, Hq=32, Hkv=8, D=128, d=4096)
     med = {key: sorted(t)[len(t) // 2] for key, t in times.items()}
     emit(f"T {T:6d}  ring {n} sets of {per_set / 2 ** 20:.0f} MiB")
     for key in fns:
-        emit(f"    {key:14s} {med[key]:10.1f} us  ({min(times[key]):.1f} .. {max(times[key]):.1f})")
-    lo, hi = min(times["fixed fwd+bwd"]) / med["fixed fwd+bwd"], max(times["fixed fwd+bwd"]) / med["fixed fwd+bwd"]
-    ratio = med["gated fwd+bwd"] / med["fixed fwd+bwd"]
-    emit(f"    gated / fixed: {ratio:.3f}; the fixed call's own spread is {lo:.3f} .. {hi:.3f}: "
+        emit(f"    {key:16s} {med[key]:10.1f} us  ({min(times[key]):.1f} .. {max(times[key]):.1f})")
+    lo, hi = min(times[base]) / med[base], max(times[base]) / med[base]
+    ratio = med["chgate fwd+bwd" if rank else "gated fwd+bwd"] / med[base]
+    emit(f"    {'per-channel / scalar-gated' if rank else 'gated / fixed'}: {ratio:.3f}; the {base.split()[0]} call's own "
+         f"spread is {lo:.3f} .. {hi:.3f}: "
          f"{'outside' if ratio > hi or ratio < lo else 'inside'} it")
     del sets
     torch.cuda.empty_cache()
@@ -155,6 +196,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--ring-mib", type=int, default=320)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--gate-rank", type=int, default=0,
+                    help="measure the per-channel gate of this rank (--linear-attn-gate-rank) against the scalar-gated calls")
     ap.add_argument("--gate", action="store_true",
                     help="measure one layer's mixer under --linear-attn-gate against the fixed-decay calls instead")
     a = ap.parse_args()
@@ -163,6 +206,21 @@ def main():
     def emit(s):
         print(s, flush=True)
         lines.append(s)
+    if a.gate_rank:
+        emit(f"# scripts/bench_linear_attn.py --gate-rank {a.gate_rank}: per-channel gated linear attention "
+             "(csrc/linear_attn_chgate.hip: gate_fwd,")
+        emit("# the mixer's fwd and bwd, gate_bwd with dW2 and the in-place dxn term, dW1) against the scalar-gated calls "
+             "in the same process,")
+        emit(f"# M7B head shape (B 1, Hq 32, Hkv 8, D 128, n_embd 4096, bf16), {torch.cuda.get_device_name(0)}; medians of "
+             f"{a.rounds}")
+        emit(f"# interleaved rounds of {a.iters} calls (min .. max), operand rings of more than {a.ring_mib} MiB.")
+        for T in (int(t) for t in a.seq_lens.split(",")):
+            run_gate(T, a.iters, a.rounds, a.ring_mib, emit, rank=a.gate_rank)
+        emit("# not measured: the end-to-end step under --linear-attn-gate-rank, loss curves, several GPUs")
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.gate:
         emit("# scripts/bench_linear_attn.py --gate: gated linear attention (csrc/linear_attn_gate.hip: gate_fwd, gated fwd,")
         emit("# gated bwd, gate_bwd with the in-place dxn term, the gate's weight gradient) against the fixed-decay fwd + bwd,")
